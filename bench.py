@@ -3,6 +3,7 @@
 GCN d=256 on 100M-edge scale-free").
 
     python bench.py --gpus 1 --steps 50 --warmup 20
+    python bench.py --gpus 1 --steps 50 --warmup 20 --dump-outputs DIR   # + a fixed sample of the last step's Y as DIR/*.npy
     python bench.py --gpus N --steps K --warmup W          # no launcher: bench.py starts its N ranks itself
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W [--mode step]
@@ -42,8 +43,11 @@ import torch
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
+HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak
 METRIC = "aggregated edges/sec + achieved HBM GB/s, GCN d=256 on 100M-edge scale-free"
+DUMP_BYTES = 32 << 20   # --dump-outputs: bytes of Y written (the cap is 64 MB)
+DUMP_HUB_ROWS = 256
+DUMP_SEED = 2024
 
 
 def algorithmic_bytes(n, nnz, d, weighted):
@@ -135,6 +139,25 @@ def pmc_traffic(workload):
     return None, None
 
 
+def dump_outputs(out_dir, g, y):
+    """--dump-outputs: Y = A_hat X as the timed launch returned it, for comparing two builds output for output.  Y is
+    n x d (10 GB at the default size), so a fixed sample of its rows is written: the DUMP_HUB_ROWS rows with the most
+    stored entries (ties by row number; the hub path of the kernel) and a seeded uniform sample of all rows, sorted.
+        y_sample.npy       float32 [rows, d]   those rows of Y
+        y_sample_rows.npy  float64 [rows]      their row numbers"""
+    import numpy as np
+    n, d = y.shape
+    deg = (g.rowptr[1:] - g.rowptr[:-1]).long()
+    hubs = torch.sort(deg, descending=True, stable=True).indices[:min(n, DUMP_HUB_ROWS)].cpu()
+    k = max(0, min(n, DUMP_BYTES // (4 * d)) - hubs.numel())
+    uniform = torch.randperm(n, generator=torch.Generator().manual_seed(DUMP_SEED))[:k]
+    rows = torch.unique(torch.cat([hubs, uniform]))                      # sorted, no repeats
+    sample = y[rows.to(y.device)].cpu()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "y_sample.npy"), sample.numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "y_sample_rows.npy"), rows.numpy().astype(np.float64))
+
+
 def _ms(fn, reps=3):
     fn()
     a0, a1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -190,6 +213,8 @@ def run_aggregate(args, rank, world, dev):
     torch.cuda.synchronize()
     D.barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, g, y)            # before the side legs below write into y
     dt = D.all_reduce_max(dt, dev)
     total_nnz = D.all_reduce_sum(g.nnz, dev)
     per_step = sorted(s.elapsed_time(e) for s, e in zip(starts, stops))
@@ -416,9 +441,16 @@ def main():
     ap.add_argument("--step-model", choices=["idgcn", "idgin"], default="idgcn")
     ap.add_argument("--step-nodes", type=int, default=2_000_000, help="step: nodes of the base graph the ego nets are cut from")
     ap.add_argument("--step-steps", type=int, default=20, help="timed steps of the `step` object in --mode both")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write what the last one computed (a fixed sample of rank 0's Y = A_hat X) "
+                         "as DIR/<name>.npy; aggregate path only")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if args.dump_outputs and args.mode == "step":
+        raise SystemExit("--dump-outputs writes the aggregate path's output: use --mode aggregate, both or auto")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         # no launcher set the ranks up: be the launcher (before anything in this process touches the GPU)

@@ -2,7 +2,7 @@
 # kernel-trace + PMC passes of scripts/agg_forms_ab.py (sum / max / two-branch, tile and plan-based); usage: prof_agg_forms.sh <tag>
 set -o pipefail
 TAG=${1:-r04}
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$REPO/gpurun_out/prof_af_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

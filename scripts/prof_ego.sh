@@ -1,6 +1,6 @@
 #!/bin/bash
 # per-kernel times of the ego-net expansion (scripts/ego_probe.py) -> gpurun_out/prof_ego/
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$REPO/gpurun_out/prof_ego
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

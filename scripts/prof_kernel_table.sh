@@ -2,7 +2,7 @@
 # PMC passes of scripts/kernel_table.py (every kernel family at the C4 shape); usage: prof_kernel_table.sh <tag>
 set -o pipefail
 TAG=${1:-r02}
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$REPO/gpurun_out/prof_kt_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

@@ -3,7 +3,7 @@
 set -o pipefail
 TAG=${1:-r01}
 SCRIPT=${2:-scripts/layer_profile.py}
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$REPO/gpurun_out/layer_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

@@ -4,7 +4,7 @@
 # Counters in their own --pmc passes (no trace domains beside them).  usage: prof_mfma_table.sh <tag>
 set -o pipefail
 TAG=${1:-r04}
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$REPO/gpurun_out/prof_mfma_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

@@ -2,7 +2,7 @@
 # rocprofv3 kernel trace of one model's training step (scripts/model_profile.py); usage: prof_model.sh KIND [NODES] [DIM]
 set -o pipefail
 KIND=${1:-gcn}; export KIND; export NODES=${2:-10000000}; export DIM=${3:-256}
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$REPO/gpurun_out/model_$KIND
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

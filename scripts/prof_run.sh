@@ -3,7 +3,7 @@
 # usage: scripts/prof_run.sh <tag>   -> gpurun_out/prof_<tag>/{trace,fetch,write}
 set -o pipefail
 TAG=${1:-r01}
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

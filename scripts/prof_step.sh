@@ -4,7 +4,7 @@ set -o pipefail
 TAG=${1:-r04}
 MODEL=${2:-idgcn}
 CEN=${3:-4096}
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$REPO/gpurun_out/prof_step_${TAG}_$MODEL
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

@@ -5,7 +5,7 @@
 PARITY UNPINNED: the reference ships no golden tensors and cannot be imported here
 (DESIGN.md §3), so these vectors are outputs of oracle/ (the op-for-op restatement of
 its CPU path), frozen so that (a) the oracle cannot drift silently and (b) the GPU box,
-which has no /root/reference, checks against fixed data.  The input graphs are synthetic
+which has no reference checkout, checks against fixed data.  The input graphs are synthetic
 graphs of the shape of the reference's bundled datasets (64-node
 networkx.powerlaw_cluster_graph, datasets/syn_graph.py:42) — the bundled *.pkl files are
 pickles and are deliberately not loaded.

@@ -1,4 +1,6 @@
-"""Fixture generator (build container only; /root/reference does not travel to the GPU box).
+"""Fixture generator (needs a checkout of the reference GraphGym).
+
+    python tests/golden/make_ref_ckpt.py <reference checkout>
 
 The reference holds two trained checkpoints written by graphgym/checkpoint.py:43-53:
 
@@ -23,7 +25,6 @@ import numpy as np
 import torch
 import yaml
 
-REF = "/root/reference/run/results"
 HERE = os.path.dirname(os.path.abspath(__file__))
 RUNS = {"ref_ckpt_node": "node/1", "ref_ckpt_node_copy1": "node-Copy1/1"}
 CFG_KEYS = [("gnn", k) for k in ("layer_type", "layers_pre_mp", "layers_mp", "layers_post_mp", "dim_inner", "batchnorm",
@@ -33,7 +34,8 @@ CFG_KEYS = [("gnn", k) for k in ("layer_type", "layers_pre_mp", "layers_mp", "la
             ("model", "loss_fun")]
 
 
-def main():
+def main(ref):
+    REF = os.path.join(ref, "run", "results")
     for out, run in RUNS.items():
         ck = torch.load(os.path.join(REF, run, "ckpt", "999.ckpt"), weights_only=True, map_location="cpu")
         with open(os.path.join(REF, run, "config.yaml")) as f:
@@ -49,6 +51,6 @@ def main():
 
 
 if __name__ == "__main__":
-    if not os.path.isdir(REF):
-        sys.exit("the reference checkout is not present: fixtures are generated in the build container only")
-    main()
+    if len(sys.argv) != 2 or not os.path.isdir(os.path.join(sys.argv[1], "run", "results")):
+        sys.exit("usage: make_ref_ckpt.py <reference checkout containing run/results/>")
+    main(sys.argv[1])

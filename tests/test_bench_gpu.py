@@ -74,3 +74,40 @@ def test_two_ranks_without_a_launcher_one_line_with_the_step_object(dev):
               "ms_per_step_fresh_batch"):
         assert k in st and st[k] is not None and st[k] >= 0, k
     assert 1.0 <= st["lpt_imbalance"] < 1.5
+
+
+def test_dump_outputs_hold_the_timed_steps_result(dev, tmp_path):
+    """--dump-outputs DIR: a fixed sample of rows of Y = A_hat X as the timed launch left it (written before the side legs
+    reuse the buffer), float32 / float64 .npy within 64 MB, equal to the CPU oracle on the same seeded inputs"""
+    import numpy as np
+    import torch
+    import graphgym_amd as ga
+    from graphgym_amd import graphgen
+    from oracle import ref_ops as R
+    n, d = 300000, 256
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--nodes", str(n), "--steps", "3", "--warmup", "1",
+                        "--no-cpu-baseline", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600,
+                       cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert _last_json(r.stdout)["steps"] == 3
+    files = sorted(os.listdir(out))
+    assert files == ["y_sample.npy", "y_sample_rows.npy"]
+    assert sum(os.path.getsize(out / f) for f in files) <= 64 << 20
+    y = np.load(out / "y_sample.npy")
+    rows_f = np.load(out / "y_sample_rows.npy")
+    assert y.dtype == np.float32 and rows_f.dtype == np.float64 and y.shape == (rows_f.size, d)
+    rows = torch.from_numpy(rows_f.astype(np.int64))
+    assert bool((rows[1:] > rows[:-1]).all()) and 0 <= int(rows[0]) and int(rows[-1]) < n and rows.numel() > 1000
+    # the same inputs as bench.run_aggregate builds them (rank 0)
+    ei = graphgen.ba_edge_index(n, 5, seed=12345, device=dev)
+    g = ga.CSRGraph.from_edge_index(ei, n, add_self_loops=True).gcn_norm("row")
+    x = torch.empty((n, d), dtype=torch.float32, device=dev)
+    x.uniform_(-1.0, 1.0, generator=torch.Generator(device=dev).manual_seed(7))
+    deg = (g.rowptr[1:] - g.rowptr[:-1]).long().cpu()
+    assert int(deg.argmax()) in set(rows.tolist())                  # the hub rows are part of the sample
+    dst, src, w = g.row_ids().cpu().long(), g.col.cpu().long(), g.val.cpu()
+    keep = torch.isin(dst, rows)
+    ref = R.coo_aggregate(torch.searchsorted(rows, dst[keep]), src[keep], w[keep], x.cpu(), rows.numel(), "sum")
+    err = float((torch.from_numpy(y) - ref).abs().max())
+    assert err <= 1e-5 * max(1.0, float(ref.abs().max())), err

@@ -127,6 +127,19 @@ def test_bench_refuses_to_run_without_a_gpu():
     assert r.returncode != 0 and "no CPU path" in (r.stderr + r.stdout)
 
 
+def test_bench_rejects_a_step_count_below_one_and_a_dump_without_the_aggregate_path():
+    """--steps is the number of timed steps (at least one); --dump-outputs writes the aggregate path's output only.
+    Both are refused before anything touches the GPU"""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for extra, msg in ((["--steps", "0"], "--steps must be >= 1"),
+                       (["--mode", "step", "--dump-outputs", "unused"], "--dump-outputs")):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + extra, capture_output=True, text=True,
+                           timeout=300, cwd=root)
+        assert r.returncode != 0 and msg in r.stderr, r.stderr[-2000:]
+
+
 def test_order_choice_and_fused_shape_gate(monkeypatch):
     """'auto' gathers at the narrower width and aggregates first at equal widths where the one-kernel
     aggregate -> transform applies; the shape gate and its MP_FUSED=0 switch are host logic"""

@@ -1,54 +1,74 @@
-"""Boundary check against the reference's real registry module, where it is present.
+"""Boundary check of the registry binding: the plugin lands in GraphGym's own ``layer_dict`` when GraphGym is importable.
 
-graphgym/register.py imports in this container; the hot-path modules do not.  Run in a
-subprocess with the reference on PYTHONPATH so that graphgym_amd.registry binds to the reference's own
-``layer_dict`` — the object GeneralLayer resolves layer_type keys from (graphgym/models/layer.py:24,238).
-Skipped on the GPU box, where /root/reference does not exist."""
+graphgym_amd.registry binds, at import, to ``graphgym.register.layer_dict`` — the object GeneralLayer resolves layer_type
+keys from (graphgym/models/layer.py:24,238).  The test runs a fresh interpreter with a stand-in ``graphgym.register`` on
+PYTHONPATH (a module-level ``layer_dict`` and a ``register_layer`` that refuses duplicates: the interface the binding
+uses) and checks that the engine's keys land in that very dictionary.  The duplicate-key messages are pinned by what the
+reference's register.py:6-10 raises, stored in tests/golden/reference_register.json (make_register_golden.py)."""
 import json
 import os
 import subprocess
 import sys
 
-import pytest
-
-REF = "/root/reference"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden", "reference_register.json")
+
+STAND_IN = r"""
+layer_dict = {}
+
+
+def register_layer(key, module):
+    if key in layer_dict:
+        raise KeyError(key)
+    layer_dict[key] = module
+"""
 
 SCRIPT = r"""
 import json, sys
-import graphgym.register as ref                      # the reference's module, unmodified
+import graphgym.register as ref                      # the stand-in GraphGym registry
 import graphgym_amd.registry as ours
 import graphgym_amd.graphgym_plugin as plugin
 out = {}
+out["have_graphgym"] = ours.HAVE_GRAPHGYM
 out["same_dict_object"] = ours.layer_dict is ref.layer_dict
 out["keys_in_reference_dict"] = sorted(k for k in plugin.ALL_KEYS if ref.layer_dict.get(k) is plugin.ALL_KEYS[k])
 try:
-    ref.register_layer("gcnidconv", object)          # the reference's own duplicate check now sees our entry
+    ref.register_layer("gcnidconv", object)          # GraphGym's own duplicate check now sees our entry
     out["dup"] = None
-except KeyError as e:
-    out["dup"] = str(e)
+except KeyError:
+    out["dup"] = True
+msgs = {}
+for key in sys.argv[1:]:
+    try:
+        ours.register(key, 1, {key: 0})
+    except KeyError as e:
+        msgs[key] = str(e)
 try:
-    ours.register("x", 1, {"x": 0})
+    ours.register_layer("gcnidconv", object)          # through the shared dictionary
 except KeyError as e:
-    out["ours_msg"] = str(e)
-try:
-    ref.register("x", 1, {"x": 0})
-except KeyError as e:
-    out["ref_msg"] = str(e)
+    out["ours_dup_msg"] = str(e)
+out["ours_msgs"] = msgs
 layer = ref.layer_dict["Tfg-idgcn"](8, 16, bias=True)
 out["params"] = sorted(n for n, _ in layer.named_parameters())
 print(json.dumps(out))
 """
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "graphgym")), reason="reference checkout not present")
-def test_plugin_lands_in_the_reference_registry():
-    env = dict(os.environ, PYTHONPATH=os.pathsep.join([ROOT, REF]))
-    r = subprocess.run([sys.executable, "-c", SCRIPT], env=env, capture_output=True, text=True, timeout=120)
+def test_plugin_lands_in_the_reference_registry(tmp_path):
+    with open(GOLDEN) as f:
+        ref_msgs = json.load(f)["duplicate_key_error"]
+    pkg = tmp_path / "graphgym"
+    pkg.mkdir()
+    (pkg / "__init__.py").write_text("")
+    (pkg / "register.py").write_text(STAND_IN)
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([str(tmp_path), ROOT]))
+    r = subprocess.run([sys.executable, "-c", SCRIPT] + sorted(ref_msgs), env=env, capture_output=True, text=True,
+                       timeout=120, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads(r.stdout.strip().splitlines()[-1])
-    assert out["same_dict_object"]
+    assert out["have_graphgym"] and out["same_dict_object"]
     assert len(out["keys_in_reference_dict"]) == 18
-    assert out["dup"] is not None and "already pre-defined" in out["dup"]
-    assert out["ours_msg"] == out["ref_msg"]          # identical KeyError text (register.py:8)
+    assert out["dup"] is True
+    assert out["ours_msgs"] == ref_msgs                # identical KeyError text (register.py:8)
+    assert out["ours_dup_msg"] == ref_msgs["gcnidconv"]
     assert out["params"] == ["model.bias", "model.kernel", "model.kernel_id"]
