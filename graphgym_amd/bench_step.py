@@ -17,7 +17,8 @@ Three cadences are timed (barrier + synchronize on both sides, max over ranks):
 and beside them the build alone (`batch_build_ms`), the exposed wait for the exchange inside the step
 (`allreduce_exposed_ms`), the exchange alone (`allreduce_ms`), the replayed step without the exchange
 (`ms_per_step_no_exchange`), and how many graph structures the timed steps had to build themselves
-(`graph_builds_inside_steps`: 0 when the pipeline prepared everything).  All timed loops run under
+(`graph_builds_inside_steps`: 0 when the pipeline prepared everything; counted on every thread but the pipeline's
+worker, so backward's builds on autograd's thread are in).  All timed loops run under
 pipeline.quiet_gc(): Python's cycle collector is kept to its young generation (a full collection is 40-80 ms).
 """
 import os
@@ -41,7 +42,7 @@ def run(args, rank, world, dev):
     import torch.nn.functional as F
 
     import graphgym_amd as ga
-    from graphgym_amd import dist as D, graph as G, graphgen, harness as H, placement
+    from graphgym_amd import dist as D, graphgen, harness as H, placement
     from graphgym_amd.pipeline import EgoBatchPipeline, quiet_gc, fit_allocator_to_changing_shapes
 
     alloc_conf = fit_allocator_to_changing_shapes()
@@ -161,11 +162,11 @@ def run(args, rank, world, dev):
             t_start = time.perf_counter()
             for k in range(steps):
                 b = p.get()
-                before = G.builds_by_this_thread()
+                before = p.builds_outside_worker()
                 th = time.perf_counter()
                 step_on(b)
                 host += time.perf_counter() - th
-                builds_in_steps += G.builds_by_this_thread() - before
+                builds_in_steps += p.builds_outside_worker() - before
                 p.done()
                 nnz += b.edges + (b.nodes if self_loops else 0)
                 nodes += b.nodes

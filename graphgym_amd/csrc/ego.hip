@@ -327,21 +327,30 @@ __global__ __launch_bounds__(kEgoBlock) void ego_edges_chunk_kernel(
     const int64_t p = m0 + i;
     const int64_t vid = v == centre32 ? c : idbase + qv - (v > centre32 ? 1 : 0);
     int64_t base = 0;
-    int has_c = 0;
+    int n_c = 0;                              // pass 1: entries from the centre in this row (parallel edges: more than one)
     if (PASS) {
       const int cw = __builtin_amdgcn_readfirstlane(cw_l[i]);
       if (!(cw & kEgoHeavyBit)) return;       // recorded in pass 0: ego_emit_light_kernel writes it
       const int64_t bl = base_l[i];
       base = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(bl >> 32)) << 32) |
                        (uint32_t)__builtin_amdgcn_readfirstlane((int)bl));
-      has_c = (cw >> 31) & 1;
+      if ((cw >> 31) & 1) {                   // the row's columns ascend: the centre's copies are one run
+        int lo = rs, hi = re;
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (((uint32_t)col[mid] & 0x7fffffffu) < centre32) lo = mid + 1; else hi = mid;
+        }
+        int e = lo;
+        while (e < re && ((uint32_t)col[e] & 0x7fffffffu) == centre32) ++e;
+        n_c = e - lo;
+      }
       if (lane == 0) {
         orig[vid] = (int64_t)v;
         if (ego_of) ego_of[vid] = (int32_t)c;
       }
     }
     int total = 0, below = 0;                 // non-centre hits so far; those with a smaller original id than v
-    bool met_c = false;
+    int met_c = 0;                            // entries from the centre so far
     uint32_t u_ahead = u_first;
     for (int j0 = rs; j0 < re; j0 += kWave) {
       const uint32_t u = u_ahead;
@@ -373,16 +382,18 @@ __global__ __launch_bounds__(kEgoBlock) void ego_edges_chunk_kernel(
       const unsigned long long mb = __ballot(hit && u < v);
       const int before = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
       if (!PASS && can_rec && q >= 0) {       // the row's first kEgoRec hits (the centre among them), in walk order
-        const int k = total + (met_c ? 1 : 0) +
+        const int k = total + met_c +
                       (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(ma >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ma, 0u));
         if (k < kEgoRec) rec[p * kEgoRec + k] = (uint16_t)q;
       }
-      met_c = met_c || __ballot(is_c) != 0ull;
+      const unsigned long long mc = __ballot(is_c);
       if (PASS && (hit || is_c)) {
-        // slot in the row: the centre first, then the other sources by new id (= by original id), the row's own self
-        // entry (LOOPS) between the smaller and the larger ones; a centre's row holds only larger ones
+        // slot in the row: the centre's entries first, then the other sources by new id (= by original id), the row's own
+        // self entry (LOOPS) between the smaller and the larger ones; a centre's row holds only larger ones
         const bool after_self = LOOPS && !is_c && (vid < B || u > v);   // (the centre's id is below every row's)
-        const int slot = is_c ? 0 : has_c + total + before + (after_self ? 1 : 0);
+        const int slot = is_c ? met_c + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mc >> 32),
+                                                                      __builtin_amdgcn_mbcnt_lo((uint32_t)mc, 0u))
+                              : n_c + total + before + (after_self ? 1 : 0);
         const int64_t hit_id = is_c ? c : idbase + q - (u > centre32 ? 1 : 0);
         const int64_t o = base + slot - (LOOPS ? vid + (after_self ? 1 : 0) : 0);      // position without the self entries
         out_dst[o] = vid;                     // row v holds v's in-edges
@@ -394,14 +405,15 @@ __global__ __launch_bounds__(kEgoBlock) void ego_edges_chunk_kernel(
       }
       total += (int)__popcll(m);
       below += (int)__popcll(mb);
+      met_c += (int)__popcll(mc);
     }
     if (!PASS && lane == 0) {
-      const bool heavy = !can_rec || total + (met_c ? 1 : 0) > kEgoRec;
-      cnt[vid] = (total + (met_c ? 1 : 0) + (LOOPS ? 1 : 0)) | (met_c ? (int)0x80000000 : 0) | (heavy ? kEgoHeavyBit : 0);
+      const bool heavy = !can_rec || total + met_c > kEgoRec;
+      cnt[vid] = (total + met_c + (LOOPS ? 1 : 0)) | (met_c ? (int)0x80000000 : 0) | (heavy ? kEgoHeavyBit : 0);
       if (heavy) heavy_s = 1;
     }
     if (PASS && LOOPS && csr_col && lane == 0) {
-      const int slot = vid < B ? 0 : has_c + below;
+      const int slot = vid < B ? 0 : n_c + below;
       csr_col[base + slot] = (int32_t)vid;
       csr_eid[base + slot] = -1 - (int32_t)vid;
     }
@@ -466,15 +478,17 @@ __global__ __launch_bounds__(kBlock) void ego_emit_light_kernel(
     if (cw & kEgoHeavyBit) continue;          // the chunk kernel's pass 1 writes it
     orig[vid] = (int64_t)v;
     if (ego_of) ego_of[vid] = (int32_t)c;
-    const int has_c = (cw >> 31) & 1;
-    const int H = (cw & 0x3fffffff) - (LOOPS ? 1 : 0);      // recorded hits, the centre among them
+    const int H = (cw & 0x3fffffff) - (LOOPS ? 1 : 0);      // recorded hits, the centre's entries among them
+    int n_c = 0;                                             // (parallel edges from the centre: more than one)
+    if ((cw >> 31) & 1)
+      for (int k = 0; k < H; ++k) n_c += rec[p * kEgoRec + k] == qcc;
     const int64_t base = eoff[vid];
-    int rank = 0, below = 0;
+    int rank = 0, below = 0, i_c = 0;
     for (int k = 0; k < H; ++k) {
       const int q = rec[p * kEgoRec + k];
       const bool is_c = q == qcc;
       const bool after_self = LOOPS && !is_c && (vid < B || q > qv);
-      const int slot = is_c ? 0 : has_c + rank + (after_self ? 1 : 0);
+      const int slot = is_c ? i_c++ : n_c + rank + (after_self ? 1 : 0);
       const int64_t hit_id = id_of(q);
       const int64_t o = base + slot - (LOOPS ? vid + (after_self ? 1 : 0) : 0);
       out_dst[o] = vid;
@@ -489,7 +503,7 @@ __global__ __launch_bounds__(kBlock) void ego_emit_light_kernel(
       }
     }
     if (LOOPS && csr_col) {
-      const int slot = vid < B ? 0 : has_c + below;
+      const int slot = vid < B ? 0 : n_c + below;
       csr_col[base + slot] = (int32_t)vid;
       csr_eid[base + slot] = -1 - (int32_t)vid;
     }

@@ -13,8 +13,13 @@ last_stats = {}          # the last call's sizes (bench / tests read them): node
 
 
 def ego_batch(base, centres, radius, csr=None):
-    """Expand `centres` (LongTensor [B] on the GPU) of the symmetric graph `base` (CSRGraph) into the
-    disjoint union of their radius-`radius` ego nets.
+    """Expand `centres` (LongTensor [B] on the GPU) of the graph `base` (CSRGraph in the engine's convention: row r holds
+    the in-edges of r, from_edge_index's default dst_row=1) into the disjoint union of their radius-`radius` ego nets.
+
+    Direction: as nx.ego_graph on a DiGraph (transform.py:19), an ego holds what its centre REACHES along the edges
+    (successors) within `radius` hops, with every edge of the base between two members, parallel edges and self loops
+    included.  A base that is not its own transpose (directed, or with repeated entries: base.is_symmetric(run=True),
+    run once per base graph and cached) is expanded over its transposed CSR (row u = out-edges of u, cached on `base`).
 
     Returns (edge_index [2, E] int64 in PyG convention, orig_node [N'] int64, node_id_index [B] int64,
     ego_of_node [N'] int32): node k of the expanded graph is original node orig_node[k]; the centres
@@ -23,8 +28,9 @@ def ego_batch(base, centres, radius, csr=None):
     csr = "none" | "add": a fifth value, the batch's CSRGraph itself — what CSRGraph.from_edge_index(edge_index, N')
     (csr="none") or from_edge_index(..., add_self_loops=True) (csr="add") would build, entry for entry, written by the
     expansion in the engine's CSR order instead of being sorted out of the COO list again; the graph is flagged
-    symmetric (an induced subgraph of a symmetric graph: its transpose is itself).  Needs a base graph without explicit
-    self loops and radius <= 4 (otherwise the fifth value is None and the caller builds the CSR the usual way).
+    symmetric (an induced subgraph of a symmetric graph: its transpose is itself) and id_branch(node_id_index) takes the
+    ego-batch shortcut.  Needs a symmetric base graph (no repeated entry) without explicit self loops, and radius <= 4;
+    otherwise the fifth value is None and the caller builds the CSR the usual way.
 
     Work and memory follow the ego nets (members + candidate neighbours of one level at a time; nothing is sized by the
     base graph): the engine asks for its buffers through a callback that hands out torch tensors on the current stream
@@ -53,14 +59,18 @@ def ego_batch(base, centres, radius, csr=None):
 
     alloc_cb, free_cb = ALLOC_FN(_alloc), FREE_FN(_free)
     res = EgoResult()
+    # the expansion walks rows and emits each member's row entries as (entry -> member) edges: on a symmetric base both
+    # directions coincide, otherwise it walks A^T (out-edges) and its edges come out reversed (flipped below)
+    symmetric = base.nnz == 0 or base.is_symmetric(run=True)
+    walk = base if symmetric else base.transpose()
     flags = 0
     if csr is not None:
         if csr not in ("none", "add"):
             raise ValueError("csr must be None, 'none' or 'add'")
-        if int(radius) <= 4 and not base.has_self_loops():
+        if int(radius) <= 4 and symmetric and not base.has_self_loops():
             flags = FLAG_CSR | (FLAG_CSR_SELF_LOOPS if csr == "add" else 0)
     with torch.cuda.device(dev):
-        status = L.mp_ego_expand(ptr(base.rowptr), ptr(base.col), N, ptr(cen), B, int(radius), flags, alloc_cb, free_cb,
+        status = L.mp_ego_expand(ptr(walk.rowptr), ptr(walk.col), N, ptr(cen), B, int(radius), flags, alloc_cb, free_cb,
                                  None, C.byref(res), _stream())
     held.clear()
     # (the ctypes callback objects and the closures they wrap form reference cycles: without this the `outs` dictionary —
@@ -74,6 +84,8 @@ def ego_batch(base, centres, radius, csr=None):
     check(status, "mp_ego_expand")
     n_out, e_out = int(res.n_nodes), int(res.n_edges)
     ei = outs[TAG_EDGES].view(torch.int64)[:2 * e_out].view(2, e_out)      # row 0 = source, row 1 = destination
+    if not symmetric:
+        ei = ei.flip(0)                                                     # (expanded over A^T: rows were sources)
     orig = outs[TAG_ORIG].view(torch.int64)[:n_out]
     ego_of = outs[TAG_EGO_OF].view(torch.int32)[:n_out]
     last_stats.clear()

@@ -34,15 +34,25 @@ def _require_hip(t, name):
 
 BUILDS = collections.Counter()   # structures built so far, by kind: a step that runs on a PREPARED batch (CSRGraph.warm) adds none
 BUILDS_BY_THREAD = collections.Counter()     # the same by building thread (the batch pipeline builds on a worker thread)
+_BUILDS_LOCK = threading.Lock()              # (backward runs on autograd's device thread, a pipeline builds on its worker)
 
 
 def _built(kind):
-    BUILDS[kind] += 1
-    BUILDS_BY_THREAD[threading.get_ident()] += 1
+    with _BUILDS_LOCK:
+        BUILDS[kind] += 1
+        BUILDS_BY_THREAD[threading.get_ident()] += 1
 
 
 def builds_by_this_thread():
-    return BUILDS_BY_THREAD[threading.get_ident()]
+    with _BUILDS_LOCK:
+        return BUILDS_BY_THREAD[threading.get_ident()]
+
+
+def builds_outside(threads=()):
+    """structures built so far by every thread except `threads` (thread idents): a training step's own builds,
+    backward (autograd's device thread) included, without those of a batch pipeline's worker"""
+    with _BUILDS_LOCK:
+        return sum(c for t, c in BUILDS_BY_THREAD.items() if t not in threads)
 
 
 _HANDLES = weakref.WeakValueDictionary()     # int handle -> CSRGraph: how a graph crosses the torch.ops.mp.* boundary
@@ -63,7 +73,7 @@ class CSRGraph:
         self.rowptr = rowptr      # [N+1] int32
         self.col = col            # [nnz] int32 (view of a capacity-sized buffer)
         self.val = val            # [nnz] fp32 or None (= ones)
-        self.eid = eid            # [nnz] int32 input position / -1-i for inserted loops, or None
+        self.eid = eid            # [nnz] int32 input position / -1-i for inserted loops, or None (see the property)
         self.num_nodes = int(num_nodes)
         self.nnz = int(nnz)
         self._plan = None
@@ -73,6 +83,19 @@ class CSRGraph:
         self.pos = None           # for a transposed graph: index into the source CSR
         self.dinv = None
         self.symmetric = False    # pattern AND values equal their transpose (ego batches of a symmetric graph): A^T is A
+
+    @property
+    def eid(self):
+        """[nnz] int32: position in the input edge_index of every stored entry, -1 - i for an inserted self loop; or
+        None.  A graph may carry a recipe for it instead (layers.seed_graph_cache: the positions under the other
+        edge_index convention), run on the first read."""
+        if self._eid is None and self._eid_recipe is not None:
+            self._eid, self._eid_recipe = self._eid_recipe(), None
+        return self._eid
+
+    @eid.setter
+    def eid(self, v):
+        self._eid, self._eid_recipe = v, None
 
     # ---- construction ----------------------------------------------------
     @classmethod
@@ -183,7 +206,8 @@ class CSRGraph:
 
     def with_values(self, val):
         """same sparsity pattern (and plan / transpose pattern), other entry values"""
-        g = CSRGraph(self.rowptr, self.col, val, self.eid, self.num_nodes, self.nnz, self.num_cols)
+        g = CSRGraph(self.rowptr, self.col, val, self._eid, self.num_nodes, self.nnz, self.num_cols)
+        g._eid_recipe = self._eid_recipe          # (not run here: the new graph reads it when it needs it)
         g._plan = self._plan
         g._row_ids = getattr(self, "_row_ids", None)
         g._pattern_of = self if getattr(self, "_pattern_of", None) is None else self._pattern_of

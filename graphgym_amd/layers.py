@@ -84,16 +84,37 @@ def get_graph(holder, edge_index, num_nodes, *, dst_row=1, loops="none", norm=No
 def seed_graph_cache(holder, edge_index, num_nodes, g, loops):
     """Put a CSRGraph that was built together with the batch (ego.ego_batch(csr=...): the expansion writes the batch's
     CSR directly) where get_graph looks for it.  `loops`: "none" (the entries of edge_index) or "add" (+ one self entry
-    per node).  The graph must be symmetric and loop-free apart from the added entries, so every self-loop policy that
-    coincides on such an input and both edge_index conventions map to it."""
+    per node).
+
+    Contract: `g` is what from_edge_index(edge_index, num_nodes, dst_row=1, ...) builds, entry for entry, eid included,
+    and is flagged symmetric (no repeated entry, A^T = A) and loop-free apart from the added entries.  Then every
+    self-loop policy that coincides on such an input maps to it, and so does the dst_row=0 convention — except for
+    `eid`, the entry's position in edge_index, which under dst_row=0 is the position of the REVERSE edge: the dst_row=0
+    keys hold a graph of the same operator (shared plan and caches) whose eid is remapped on its first read."""
+    if not g.symmetric:
+        raise ValueError("seed_graph_cache needs a graph flagged symmetric (ego.ego_batch returns None otherwise)")
     stamp = (edge_index.data_ptr(), tuple(edge_index.shape), edge_index._version, int(num_nodes))
     cache = {"stamp": stamp, "edge_index": edge_index}
+    g0 = g.with_values(g.val)
+    g0.symmetric = True
+    g0.eid = None
+    g0._eid_recipe = lambda: _eid_of_the_other_convention(g)
     same = ("none", "remove") if loops == "none" else ("add", "remaining", "remove_add")
-    for dst_row in (0, 1):
+    for dst_row, gd in ((0, g0), (1, g)):
         for lp in same:
-            cache[(dst_row, lp, None, 1.0)] = g
+            cache[(dst_row, lp, None, 1.0)] = gd
     setattr(holder, "_mp_graph_cache", cache)
     return cache
+
+
+def _eid_of_the_other_convention(g):
+    """eid of a symmetric CSR without repeated entries (columns ascending within a row) read under the other edge_index
+    convention: entry (r, c) of one is entry (c, r) of the other, found by a binary search over the sorted (row, col)
+    keys; an inserted self entry (eid < 0) maps to itself"""
+    if g.eid is None or g.nnz == 0:
+        return g.eid
+    r, c, n = g.row_ids().long(), g.col.long(), g.num_nodes
+    return g.eid[torch.searchsorted(r * n + c, c * n + r)]
 
 
 def _is_relu(fn):

@@ -26,6 +26,7 @@ import collections
 import contextlib
 import gc
 import os
+import threading
 import time
 import types
 
@@ -42,7 +43,7 @@ class EgoBatch(types.SimpleNamespace):
 
 class EgoBatchPipeline:
     def __init__(self, base, features, radius, prepare=None, device=None, threaded=True, csr=None):
-        """base: CSRGraph of the (symmetric) base graph; features: [N, F] node features of the base graph;
+        """base: CSRGraph of the base graph; features: [N, F] node features of the base graph;
         prepare(inputs, holder): builds the model's per-batch graph structures (e.g. TfgNodeModel.prepare);
         threaded: the build runs on a worker THREAD as well as on its own stream — the step's launches are host work too
         (an ID-GCN step on a 2 * 10^6-node batch is ~150 launches), and one Python thread would enqueue step and build one
@@ -51,6 +52,10 @@ class EgoBatchPipeline:
         self.base, self.features, self.radius, self.prepare = base, features, int(radius), prepare
         self.csr = csr      # "none" | "add": let the expansion write the batch's CSR itself (ego.ego_batch(csr=...))
         self.device = device if device is not None else base.device
+        # the expansion asks whether the base is its own transpose (once per graph, cached: one pass over its entries) and
+        # walks the transpose when it is not: both are done here, on the caller's thread, not inside a build or a step
+        if base.nnz and not base.is_symmetric(run=True):
+            base.transpose()
         # a HIGH-PRIORITY stream: the build is many short launches separated by size reads; queued at normal priority
         # behind the step's long HBM-bound launches every one of those reads waits for a slot (build 7.5 ms alone, ~18 ms
         # beside a step), at high priority its launches take the next free compute units
@@ -71,9 +76,17 @@ class EgoBatchPipeline:
         from . import placement
         placement.pause()
         self._paused = True
+        self._workers = set()              # ident of the worker thread (builds_outside_worker leaves its builds out)
         if threaded:
             import concurrent.futures
-            self._pool = concurrent.futures.ThreadPoolExecutor(max_workers=1, thread_name_prefix="mp-batch")
+            self._pool = concurrent.futures.ThreadPoolExecutor(max_workers=1, thread_name_prefix="mp-batch",
+                                                               initializer=lambda: self._workers.add(threading.get_ident()))
+
+    def builds_outside_worker(self):
+        """graph structures built so far by every thread but this pipeline's worker: the caller's own and autograd's
+        (backward runs on a device thread of its own).  The difference across a training step is what the step built —
+        0 on a prepared batch — however far ahead the worker is building."""
+        return G.builds_outside(self._workers)
 
     def submit(self, centres, labels):
         """start building the batch around `centres` (LongTensor [B], HOST) with labels `labels` ([B], HOST) on the side
