@@ -15,9 +15,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(CSRC, "libmpengine.so")
-SOURCES = ["spmm.hip", "fused.hip", "csr_build.hip", "attn.hip", "ego.hip", "gemm.hip", "dense_x3.hip", "bn.hip", "util.hip", "probe.hip", "loss.hip"]
+SOURCES = ["spmm.hip", "fused.hip", "fused_hot.hip", "csr_build.hip", "attn.hip", "ego.hip", "gemm.hip", "dense_x3.hip", "bn.hip", "util.hip", "probe.hip", "loss.hip"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "vecio.h"), os.path.join(CSRC, "bf16x3.h"), os.path.join(ROOT, "include", "mp_engine.h")]
 ARCH = "gfx950"
+# per-source flags.  fused_hot.hip (the hot kernels of fused.hip alone): uniform branches stay branches, not structurized
+# into two one-sided regions — the gather's per-row choice of cache policy otherwise leaves control-flow paths with zero
+# or two loads, and the wait counting falls back to vmcnt(0) at every consumed row (see the file)
+EXTRA_FLAGS = {"fused_hot.hip": ["-mllvm", "-structurizecfg-skip-uniform-regions=true"]}
 
 
 def _hipcc():
@@ -45,7 +49,7 @@ def build(force=False, verbose=True):
         obj = os.path.join(CSRC, s.replace(".hip", ".o"))
         objs.append(obj)
         cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-c",
-               os.path.join(CSRC, s), "-o", obj]
+               os.path.join(CSRC, s), "-o", obj] + EXTRA_FLAGS.get(s, [])
         if verbose:
             print(" ".join(cmd), flush=True)
         procs.append((s, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))

@@ -676,8 +676,12 @@ __device__ __forceinline__ void mfma_rows(const float (*T)[FH + 4], const float*
 // walking K together (eight consumers would need 12 waves of <= 168 registers and spill).  HAS_S: the self-term form.
 // AGG_ONLY: no product — the consumers store the aggregated rows (a.P) and nothing else: the aggregation itself on
 // this kernel's structure (mp_agg_rows_tiles_f32 below).
+// HOT (AGG_ONLY): the column indices carry a tag in their sign bit (mp_agg_rows_tiles_hot_f32): a tagged column's row
+// of X is gathered with the default cache policy, every other row non-temporal, so that the most-used rows can stay in
+// the caches while the cold rows stream past them.  Same terms, same order: the same bits as HOT = false.  Instantiated
+// only in fused_hot.hip (a translation unit of its own, built with other compiler flags: see there).
 template <int W, bool WEIGHTED, int U, int KH, int NCB, int PF, bool NT_OUT, bool BF16X3, int TR, int NP, int NC, bool HAS_S,
-          bool AGG_ONLY = false, bool MAXR = false>
+          bool AGG_ONLY = false, bool MAXR = false, bool HOT = false>
 __global__ __launch_bounds__((NP + NC) * kWave, TR == 64 ? (NP + NC + 3) / 4 : 4)
 void agg_dense_pc_kernel(FusedArgs a, unsigned int* __restrict__ tile_ctr, int32_t n_tiles) {
   constexpr int FH = kWave * W;
@@ -691,6 +695,8 @@ void agg_dense_pc_kernel(FusedArgs a, unsigned int* __restrict__ tile_ctr, int32
   // MAXR: the rows' maximum of w_ij x[j] instead of their sum (AGG_ONLY, no self term; a row without entries is 0 as in
   // spmm.hip's finish_row).  A maximum does not depend on the order of its terms: same bits as the plan-based kernel.
   static_assert(!MAXR || (AGG_ONLY && !HAS_S), "the maximum is an aggregation-only form");
+  static_assert(!HOT || AGG_ONLY, "the hot-column tag is an aggregation-only form");
+  constexpr int kIdxMask = HOT ? -1 : 0x7fffffff;   // HOT: the tag travels to the gather (an identity mark is not part of the index)
   constexpr float kInit = MAXR ? -INFINITY : 0.f;
   __shared__ __attribute__((aligned(16))) float T[2][kTileRows][LDT];
   __shared__ __attribute__((aligned(16))) float carry[kPcGather - 1][FH];
@@ -760,6 +766,13 @@ void agg_dense_pc_kernel(FusedArgs a, unsigned int* __restrict__ tile_ctr, int32
       return r;
     };
     auto rp_at = [&](int rp, int end, int r) { return r >= kTileRows ? end : bcast_i(rp, r); };   // r: wave-uniform
+    // HOT: this lane's piece of one gathered row of X (K half kh), its column word `c` (wave-uniform: a scalar branch)
+    // tagged in the sign bit = default policy, untagged = non-temporal
+    auto load_row_tagged = [&](int kh, int c, float (&v)[W]) {
+      const float* rb = a.X + (int64_t)(c & 0x7fffffff) * a.ldx + kh * FH;
+      if (c < 0) load_vec_row_buf<W, 0>(rb, lane * W * 4, FH * 4, v);
+      else load_vec_row_buf<W, 2>(rb, lane * W * 4, FH * 4, v);
+    };
     // this wave's quarter of a tile's entries: [s, e), the tile row its first entry lies in, and whether that row began
     // in an earlier wave's run
     auto run_of = [&](int rp, int E1, int& s_, int& e_, int& frl, bool& ct) {
@@ -916,6 +929,7 @@ void agg_dense_pc_kernel(FusedArgs a, unsigned int* __restrict__ tile_ctr, int32
               // re-reads from L2 — non-temporal loads keep them from pushing W out (round 4, in-process A/B on the same
               // buffers: 52.1 -> 51.0 ms; at F = 256, where W is 0.4 MB, no difference: left as plain loads)
               if constexpr (!AGG_ONLY && KH == 2) load_vec_nt<W>(xl + (int64_t)bcast_i(cvb, jb + j) * a.ldx, vb[j]);
+              else if constexpr (HOT) load_row_tagged(cur_kh, bcast_i(cvb, jb + j), vb[j]);
               else load_vec<W>(xl + (int64_t)bcast_i(cvb, jb + j) * a.ldx, vb[j]);
             }
           };
@@ -945,7 +959,7 @@ void agg_dense_pc_kernel(FusedArgs a, unsigned int* __restrict__ tile_ctr, int32
               }
             }
           };
-          int cvb = cvF & 0x7fffffff;   // an identity mark (sign bit) is not part of the index
+          int cvb = cvF & kIdxMask;   // an identity mark (sign bit) is not part of the index
           float wvb = wvF;
           int jb0 = 0;
           if (pre) {   // the first U rows were requested before the barriers that closed the previous item
@@ -955,7 +969,7 @@ void agg_dense_pc_kernel(FusedArgs a, unsigned int* __restrict__ tile_ctr, int32
           for (int ec = es; ec < ee; ec += kWave, jb0 = 0) {
             if (ec != es) {
               const int me = min(ec + lane, ee - 1);
-              cvb = a.col[me] & 0x7fffffff;
+              cvb = a.col[me] & kIdxMask;
               if (WEIGHTED) wvb = a.val[me];
             }
             const int n = min(kWave, ee - ec);
@@ -975,10 +989,11 @@ void agg_dense_pc_kernel(FusedArgs a, unsigned int* __restrict__ tile_ctr, int32
         pre = false;
         if (nxt_tile >= 0 && es1 < ee1) {   // the next item's first U rows travel through the barriers below
           const float* __restrict__ xl1 = a.X + nxt_kh * FH + lane * W;
-          const int c1 = cv1 & 0x7fffffff;
+          const int c1 = cv1 & kIdxMask;
 #pragma unroll
           for (int j = 0; j < U; ++j) {
             if constexpr (!AGG_ONLY && KH == 2) load_vec_nt<W>(xl1 + (int64_t)bcast_i(c1, j) * a.ldx, vb[j]);
+            else if constexpr (HOT) load_row_tagged(nxt_kh, bcast_i(c1, j), vb[j]);
             else load_vec<W>(xl1 + (int64_t)bcast_i(c1, j) * a.ldx, vb[j]);
           }
           pre = true;
@@ -1235,7 +1250,9 @@ void agg_dense_pc_kernel(FusedArgs a, unsigned int* __restrict__ tile_ctr, int32
 
 constexpr int kPcSlots = 4096;
 constexpr int kMaxDevPc = 16;
+#ifndef MP_FUSED_HOT_TU
 __device__ unsigned int g_pc_tile_ctr[kPcSlots];
+#endif
 
 constexpr int kFusedMaxGrid = 65536;
 
@@ -1260,8 +1277,11 @@ static int launch_fused_tiles(const FusedArgs& a, hipStream_t st) {   // one wor
 // could memset the counter of a launch on another stream — ADVICE r3).  A launch recorded into a HIP graph bakes its
 // slot into the graph, and graphs captured on one stream may later replay concurrently on different streams: every
 // captured launch gets a slot of its own that is never handed out again.  4096 slots per device; when they run out
-// (thousands of captured launches) the call fails with MP_ERR_UNSUPPORTED rather than share one.
-static int pc_counter(unsigned int** ctr, hipStream_t st) {
+// (thousands of captured launches) the call fails with MP_ERR_UNSUPPORTED rather than share one.  (One pool for the
+// library: fused_hot.hip calls this one.)
+int pc_counter(unsigned int** ctr, hipStream_t st);
+#ifndef MP_FUSED_HOT_TU
+int pc_counter(unsigned int** ctr, hipStream_t st) {
   static std::mutex mu;
   static unsigned int* base[kMaxDevPc] = {nullptr};
   static int next_slot[kMaxDevPc] = {0};
@@ -1297,6 +1317,7 @@ static int pc_counter(unsigned int** ctr, hipStream_t st) {
   MP_HIP(hipMemsetAsync(*ctr, 0, sizeof(unsigned int), st));
   return MP_OK;
 }
+#endif
 
 template <int W, int KH, int NCB, int PF, int TR, int NP, int NC, bool HAS_S>
 static int launch_fused_pc_s(const FusedArgs& a, hipStream_t st) {
@@ -1319,7 +1340,7 @@ static int launch_fused_pc_s(const FusedArgs& a, hipStream_t st) {
 }
 
 // the aggregation alone on the producer/consumer structure: out = reduce_j w_ij x[j] (+ self_scale * S), sum / mean
-template <int W, int KH, int TR, int NP, bool MAXR = false>
+template <int W, int KH, int TR, int NP, bool MAXR = false, bool HOT = false>
 static int launch_agg_tiles(const FusedArgs& a, hipStream_t st) {
   const int64_t n_tiles = ceil_div(a.N, TR);
   unsigned int* ctr = nullptr;
@@ -1329,10 +1350,10 @@ static int launch_agg_tiles(const FusedArgs& a, hipStream_t st) {
   const dim3 grid((unsigned)(n_tiles < resident ? n_tiles : resident)), block((NP + 4) * kWave);
   const int32_t nt = (int32_t)n_tiles;
 #define MP_AGG_TILES(WV, SV) \
-  hipLaunchKernelGGL((agg_dense_pc_kernel<W, WV, MP_FUSED_U, KH, 1, 1, true, false, TR, NP, 4, SV, true>), grid, block, 0, st, a, ctr, nt)
+  hipLaunchKernelGGL((agg_dense_pc_kernel<W, WV, MP_FUSED_U, KH, 1, 1, true, false, TR, NP, 4, SV, true, false, HOT>), grid, block, 0, st, a, ctr, nt)
   if constexpr (MAXR) {
-    if (a.val) hipLaunchKernelGGL((agg_dense_pc_kernel<W, true, MP_FUSED_U, KH, 1, 1, true, false, TR, NP, 4, false, true, true>), grid, block, 0, st, a, ctr, nt);
-    else hipLaunchKernelGGL((agg_dense_pc_kernel<W, false, MP_FUSED_U, KH, 1, 1, true, false, TR, NP, 4, false, true, true>), grid, block, 0, st, a, ctr, nt);
+    if (a.val) hipLaunchKernelGGL((agg_dense_pc_kernel<W, true, MP_FUSED_U, KH, 1, 1, true, false, TR, NP, 4, false, true, true, HOT>), grid, block, 0, st, a, ctr, nt);
+    else hipLaunchKernelGGL((agg_dense_pc_kernel<W, false, MP_FUSED_U, KH, 1, 1, true, false, TR, NP, 4, false, true, true, HOT>), grid, block, 0, st, a, ctr, nt);
   } else {
     if (a.val) { if (a.S) MP_AGG_TILES(true, true); else MP_AGG_TILES(true, false); }
     else { if (a.S) MP_AGG_TILES(false, true); else MP_AGG_TILES(false, false); }
@@ -1396,6 +1417,7 @@ static int launch_fused(const FusedArgs& a, hipStream_t st) {
 // out[rows[k], :] = act(out[rows[k], :] + sum_{e in [crp[k], crp[k+1])} val[e] * Z[slot[e], :]) — one wave per
 // listed row (a few entries each), columns in 16-byte pieces where the alignment allows
 // SET: out[rows[k], :] = the sum alone (the row's previous contents are not read)
+#ifndef MP_FUSED_HOT_TU
 template <int VW, bool SET = false>
 __global__ __launch_bounds__(kBlock) void id_fixup_kernel(const int32_t* __restrict__ rows,
                                                           const int32_t* __restrict__ crp,
@@ -1448,6 +1470,8 @@ static int launch_id_rows(const int32_t* rows, const int32_t* crp, const int32_t
   return MP_OK;
 }
 
+#endif
+
 }  // namespace mp
 
 using namespace mp;
@@ -1460,6 +1484,7 @@ int mp_debug_read(void* dst, size_t bytes) {
 }
 #endif
 
+#ifndef MP_FUSED_HOT_TU
 static int agg_dense_common(const int32_t* rowptr, const int32_t* col, const float* val, int64_t N, int reduce,
                             const float* X, int64_t ldx, int32_t F, const float* S, int64_t lds, float self_scale,
                             const float* W, int64_t ldw, int32_t d_out, const float* bias, int act,
@@ -1500,7 +1525,11 @@ static int agg_dense_common(const int32_t* rowptr, const int32_t* col, const flo
   }
 }
 
-int mp_agg_rows_tiles_f32(const int32_t* rowptr, const int32_t* col, const float* val, int64_t N, int reduce,
+#endif
+
+extern "C++" {   // (a template inside the C entry points)
+template <bool HOT>
+static int agg_rows_tiles(const int32_t* rowptr, const int32_t* col, const float* val, int64_t N, int reduce,
                           const float* X, int64_t ldx, int32_t F, const float* S, int64_t lds, float self_scale,
                           float* out, int64_t ldo, mp_stream_t stream) {
   if (!rowptr || !X || !out || N < 0 || F <= 0) return MP_ERR_INVALID_ARG;
@@ -1523,13 +1552,27 @@ int mp_agg_rows_tiles_f32(const int32_t* rowptr, const int32_t* col, const float
   a.out_vec4 = true;
   hipStream_t st = as_stream(stream);
   if (reduce == MP_MAX) {   // (values only: the argmax the backward pass needs stays with mp_spmm_f32)
-    if (F == 512) return launch_agg_tiles<4, 2, 64, 4, true>(a, st);
-    if (F == 128) return launch_agg_tiles<2, 1, 32, 4, true>(a, st);
-    return launch_agg_tiles<4, 1, 64, 4, true>(a, st);
+    if (F == 512) return launch_agg_tiles<4, 2, 64, 4, true, HOT>(a, st);
+    if (F == 128) return launch_agg_tiles<2, 1, 32, 4, true, HOT>(a, st);
+    return launch_agg_tiles<4, 1, 64, 4, true, HOT>(a, st);
   }
-  if (F == 512) return launch_agg_tiles<4, 2, 64, 4>(a, st);
-  if (F == 128) return launch_agg_tiles<2, 1, 32, 4>(a, st);   // (512-byte rows: 32-row tiles, two workgroups per CU; 64-row tiles: 13.0 vs 9.85 ms)
-  return launch_agg_tiles<4, 1, 64, 4>(a, st);
+  if (F == 512) return launch_agg_tiles<4, 2, 64, 4, false, HOT>(a, st);
+  if (F == 128) return launch_agg_tiles<2, 1, 32, 4, false, HOT>(a, st);   // (512-byte rows: 32-row tiles, two workgroups per CU; 64-row tiles: 13.0 vs 9.85 ms)
+  return launch_agg_tiles<4, 1, 64, 4, false, HOT>(a, st);
+}
+}  // extern "C++"
+
+#ifdef MP_FUSED_HOT_TU
+int mp_agg_rows_tiles_hot_f32(const int32_t* rowptr, const int32_t* col_hot, const float* val, int64_t N, int reduce,
+                              const float* X, int64_t ldx, int32_t F, const float* S, int64_t lds, float self_scale,
+                              float* out, int64_t ldo, mp_stream_t stream) {
+  return agg_rows_tiles<true>(rowptr, col_hot, val, N, reduce, X, ldx, F, S, lds, self_scale, out, ldo, stream);
+}
+#else
+int mp_agg_rows_tiles_f32(const int32_t* rowptr, const int32_t* col, const float* val, int64_t N, int reduce,
+                          const float* X, int64_t ldx, int32_t F, const float* S, int64_t lds, float self_scale,
+                          float* out, int64_t ldo, mp_stream_t stream) {
+  return agg_rows_tiles<false>(rowptr, col, val, N, reduce, X, ldx, F, S, lds, self_scale, out, ldo, stream);
 }
 
 int mp_idgnn_agg_tiles_f32(const int32_t* rowptr, const int32_t* col, const float* val, int64_t N, const float* X,
@@ -1612,5 +1655,7 @@ int mp_id_rows_f32(const int32_t* rows, const int32_t* crp, const int32_t* slot,
   if (n_rows == 0) return MP_OK;
   return launch_id_rows(rows, crp, slot, val, n_rows, Z, ldz, out, ldo, d, kNumCU * 16, as_stream(stream));
 }
+
+#endif  // MP_FUSED_HOT_TU
 
 }  // extern "C"

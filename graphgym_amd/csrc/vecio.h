@@ -36,6 +36,23 @@ template <int W> __device__ __forceinline__ void load_vec_nt(const float* p, flo
   }
 }
 
+// v[W] at byte offset `off` (< bytes) of the wave-uniform row `base`, as a buffer load with cache policy POL (0: default,
+// 2: nt on gfx950).  The policy is an operand of the instruction: the compiler merges a plain load and a
+// __builtin_nontemporal_load of the same address in the two arms of a branch into one plain load (the hint dropped),
+// but not two buffer loads of different policies.
+template <int W, int POL> __device__ __forceinline__ void load_vec_row_buf(const float* base, int off, int bytes, float (&v)[W]) {
+  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), (short)0, bytes, 0x00020000);
+  if constexpr (W == 4) {
+    const f32x4 t = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, POL));
+    v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
+  } else if constexpr (W == 2) {
+    const f32x2 t = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, POL));
+    v[0] = t[0]; v[1] = t[1];
+  } else {
+    v[0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, POL));
+  }
+}
+
 template <int W> __device__ __forceinline__ void store_vec(float* p, const float (&v)[W]);
 template <> __device__ __forceinline__ void store_vec<4>(float* p, const float (&v)[4]) {
   f32x4 t = {v[0], v[1], v[2], v[3]};

@@ -55,6 +55,30 @@ def builds_outside(threads=()):
         return sum(c for t, c in BUILDS_BY_THREAD.items() if t not in threads)
 
 
+def hot_budget_columns(budget_bytes, row_bytes):
+    """how many rows of row_bytes each fit a cache budget of budget_bytes"""
+    return max(0, int(budget_bytes) // int(row_bytes)) if row_bytes > 0 else 0
+
+
+def hot_columns(counts, H):
+    """bool mask over columns: the H columns with the most entries (any subset at a tie; every column if H >= their
+    number)"""
+    n = counts.numel()
+    hot = torch.zeros(n, dtype=torch.bool, device=counts.device)
+    if H >= n:
+        hot.fill_(True)
+    elif H > 0:
+        hot[torch.topk(counts, H, sorted=False).indices] = True
+    return hot
+
+
+def tag_hot_columns(col, hot):
+    """col | 0x80000000 on the entries whose column is marked in `hot` (int32, a new tensor)"""
+    tag = torch.zeros(hot.numel(), dtype=torch.int32, device=col.device)
+    tag.masked_fill_(hot, -2 ** 31)
+    return col | tag.index_select(0, col)
+
+
 _HANDLES = weakref.WeakValueDictionary()     # int handle -> CSRGraph: how a graph crosses the torch.ops.mp.* boundary
 _next_handle = itertools.count(1)
 
@@ -256,6 +280,31 @@ class CSRGraph:
                                            nb.value, counts, _stream()), "mp_spmm_plan_build")
             self._plan = (blob, counts)
         return self._plan
+
+    # ---- hot-column tag (mp_agg_rows_tiles_hot_f32) -------------------------
+    def hot_col(self, budget_bytes, row_bytes):
+        """a copy of col with the sign bit set on the entries whose column is among the H = budget / row_bytes most
+        used ones (their rows of X are gathered with the default cache policy, all others non-temporal), or None when
+        H = 0.  Built once per pattern and H (with_values / gcn_norm graphs share it), never under stream capture
+        (None there unless already built); col itself is never modified (the plan kernel, attention and the two-branch
+        path read it, the last with its own sign-bit marks)."""
+        H = hot_budget_columns(budget_bytes, row_bytes)
+        if H == 0 or self.nnz == 0:
+            return None
+        owner = getattr(self, "_pattern_of", None) or self
+        cache = owner.__dict__.setdefault("_hot_col", {})
+        t = cache.get(H)
+        if t is None:
+            if torch.cuda.is_available() and self.col.is_cuda and torch.cuda.is_current_stream_capturing():
+                return None
+            _built("hot_col")
+            counts = owner.__dict__.get("_col_counts")
+            if counts is None:
+                counts = torch.bincount(owner.col, minlength=owner.num_cols)
+                owner.__dict__["_col_counts"] = counts
+            t = tag_hot_columns(owner.col, hot_columns(counts, H))
+            cache[H] = t
+        return t
 
     # ---- derived graphs ----------------------------------------------------
     def has_self_loops(self):

@@ -27,7 +27,8 @@ def _raw_spmm(g, x, reduce, S=None, self_scale=0.0, bias=None, relu=False, want_
               col_override=None, out=None):
     """one launch of mp_spmm_csr_f32 — or, for plain sum / mean / max (values only, no argmax) at d = 128 / 256 / 512 on
     a large operator, of mp_agg_rows_tiles_f32 (the same aggregation on the producer/consumer tile structure: 2-5 %
-    faster; MP_AGG_TILES=0 keeps the plan-based kernel) —; x [n_src, d] -> y [N, d] (written into `out` when given)"""
+    faster; MP_AGG_TILES=0 keeps the plan-based kernel; for an X of >= AGG_HOT_MIN_BYTES its hot-column form,
+    mp_agg_rows_tiles_hot_f32: _hot_col) —; x [n_src, d] -> y [N, d] (written into `out` when given)"""
     L = lib()
     N, d = g.num_nodes, x.size(1)
     y = out if out is not None else placement.empty_or_torch((N, d), x.device, reads=(x,))
@@ -37,12 +38,19 @@ def _raw_spmm(g, x, reduce, S=None, self_scale=0.0, bias=None, relu=False, want_
             and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0 and y.stride(0) % 4 == 0 and y.data_ptr() % 16 == 0
             and (S is None or (S.stride(0) % 4 == 0 and S.data_ptr() % 16 == 0))
             and g.nnz > 0 and g.max_row_entries() <= FUSED_MAX_ROW):
-        global AGG_TILES_CALLS
+        global AGG_TILES_CALLS, AGG_HOT_CALLS
         AGG_TILES_CALLS += 1
+        col_hot = _hot_col(g, x)
         with torch.cuda.device(x.device):
-            check(L.mp_agg_rows_tiles_f32(ptr(g.rowptr), ptr(g.col), ptr(g.val), N, reduce, ptr(x), x.stride(0), d,
-                                          ptr(S), S.stride(0) if S is not None else 0, float(self_scale),
-                                          ptr(y), y.stride(0), _stream()), "mp_agg_rows_tiles_f32")
+            if col_hot is not None:
+                AGG_HOT_CALLS += 1
+                check(L.mp_agg_rows_tiles_hot_f32(ptr(g.rowptr), ptr(col_hot), ptr(g.val), N, reduce, ptr(x), x.stride(0),
+                                                  d, ptr(S), S.stride(0) if S is not None else 0, float(self_scale),
+                                                  ptr(y), y.stride(0), _stream()), "mp_agg_rows_tiles_hot_f32")
+            else:
+                check(L.mp_agg_rows_tiles_f32(ptr(g.rowptr), ptr(g.col), ptr(g.val), N, reduce, ptr(x), x.stride(0), d,
+                                              ptr(S), S.stride(0) if S is not None else 0, float(self_scale),
+                                              ptr(y), y.stride(0), _stream()), "mp_agg_rows_tiles_f32")
         return y, None
     argmax = torch.empty((N, d), dtype=torch.int32, device=x.device) if want_argmax else None
     plan, counts = g.plan()
@@ -175,6 +183,22 @@ AGG_TILES_CALLS = 0                   # launches of mp_agg_rows_tiles_f32 by thi
 AGG_TILES_WIDTHS = (128, 256, 512)   # widths of mp_agg_rows_tiles_f32 (d = 128: 10.04 -> 9.85 ms; d = 64 stays on the plan-based kernel)
 AGG_TILES_MIN_ROWS = 1 << 21    # crossover against the plan-based kernel on BA graphs (d = 256): 1e6 rows 2.15 vs 1.73 ms, 2e6 3.72 vs 3.82, 3e6 5.45 vs 5.82, 1e7 19.6 vs 20.6
 FUSED_MAX_ROW = 1 << 18      # longer rows (star-like hubs) go to the plan-based kernel, which spreads them over many waves
+AGG_HOT_CALLS = 0           # launches of mp_agg_rows_tiles_hot_f32 by this process
+AGG_HOT_MB = 256            # MP_AGG_HOT_MB (read per call; 0 = off): the rows of X kept cache-resident by the tile aggregation
+# X below this keeps the plain kernel: at d = 256, hot (256 MB) against plain, 0.25 GiB of X 1.005 vs 0.885 ms, 0.5 GiB
+# 1.485 vs 1.399, 1 GiB 2.226 vs 2.237, 9.8 GiB 18.48 vs 20.62 (profiles/r05_hot_ab_small.jsonl, r05_hot_ab.jsonl).  With
+# AGG_TILES_MIN_ROWS = 2^21 a square operator at d >= 128 is past it anyway: it decides for rectangular ones.
+AGG_HOT_MIN_BYTES = int(os.environ.get("MP_AGG_HOT_MIN_BYTES", 1 << 30))
+
+
+def _hot_col(g, x):
+    """the tagged column indices for mp_agg_rows_tiles_hot_f32 (graph.py, CSRGraph.hot_col), or None: X below
+    AGG_HOT_MIN_BYTES, a zero budget, or none built yet under stream capture"""
+    row_bytes = x.size(1) * x.element_size()
+    if x.size(0) * row_bytes < AGG_HOT_MIN_BYTES:
+        return None
+    mb = float(os.environ.get("MP_AGG_HOT_MB", AGG_HOT_MB))
+    return g.hot_col(int(mb * (1 << 20)), row_bytes) if mb > 0 else None
 
 
 def agg_dense_supported(g, x, W):

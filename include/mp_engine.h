@@ -337,6 +337,13 @@ int mp_agg_rows_tiles_f32(const int32_t* rowptr, const int32_t* col, const float
                           const float* X, int64_t ldx, int32_t F, const float* S, int64_t lds, float self_scale,
                           float* out, int64_t ldo, mp_stream_t stream);
 
+/* mp_agg_rows_tiles_f32 with cache hints in the column indices: col_hot[e] = col[e] | 0x80000000 on the entries whose
+ * source row of X should stay in the caches (the most-used columns: graph.py, CSRGraph.hot_col); those rows are
+ * gathered with the default cache policy, all others non-temporal.  Same arguments, same results bit for bit. */
+int mp_agg_rows_tiles_hot_f32(const int32_t* rowptr, const int32_t* col_hot, const float* val, int64_t N, int reduce,
+                              const float* X, int64_t ldx, int32_t F, const float* S, int64_t lds, float self_scale,
+                              float* out, int64_t ldo, mp_stream_t stream);
+
 /* The identity branch of the ID layers on top of mp_agg_dense_f32: out = act(A (X W + S X W_id) + b)
  * (gcn_id, TfgIDLayer.py:510-523; GCNIDConvLayer.forward, idconv.py:150-177) equals
  * act((A X) W + b + A_id Z) with Z = X[id] W_id (n_id rows: a small product the caller makes) and A_id the stored
