@@ -131,6 +131,13 @@ def _apply_act(h, fn):
     return fn(h)
 
 
+def _no_bf16_attention(x):
+    """the attention kernels are fp32 only: a bf16 model with an attention layer is refused, never run on a silent cast"""
+    if x.dtype == torch.bfloat16:
+        raise TypeError("the attention layers (gatconv, gatidconv, Tfg-gatconv, Tfg-idgat) do not support bfloat16: "
+                        "run them in float32")
+
+
 def _id_branch(h, x, id_index, weight_id):
     """h[id] += x[id] @ W_id  (K10)"""
     return ops.index_add_rows(h, id_index, torch.matmul(ops.gather_rows(x, id_index), weight_id))
@@ -393,6 +400,7 @@ class GATIDConvLayer(nn.Module):
         return out + self.bias if self.bias is not None else out
 
     def forward(self, x, edge_index, id, size=None, holder=None):
+        _no_bf16_attention(x)
         g = get_graph(holder, edge_index, x.size(0), loops="remove_add")
         h = ops.dense_fused(x, self.weight)
         if id is not None:
@@ -538,6 +546,7 @@ class GATConvLayer(nn.Module):
         zeros(self.bias)
 
     def forward(self, x, edge_index, holder=None):
+        _no_bf16_attention(x)
         g = get_graph(holder, edge_index, x.size(0), loops="remove_add")
         H, Cc = self.heads, self.out_channels
         h = self.lin_l(x)
@@ -678,6 +687,8 @@ class _KerasLike(nn.Module):
         if not self._built:
             self.build(x.size(-1))
             self.to(x.device)
+            if x.dtype == torch.bfloat16:     # a bf16 model built on its first call: parameters follow x
+                self.to(torch.bfloat16)
 
     def forward(self, inputs, cache=None, training=None, mask=None, holder=None):
         return self.call(inputs, cache=cache, training=training, mask=mask, holder=holder)
@@ -891,6 +902,7 @@ class IDGAT(_KerasLike):
 
     def call(self, inputs, cache=None, training=None, mask=None, holder=None):
         x, edge_index, id_index, _ = _unpack(inputs, self.with_id)     # edge_weight unused (:248-249)
+        _no_bf16_attention(x)
         self._maybe_build(x)
         H = self.num_heads
         g = get_graph(holder, edge_index, x.size(0), dst_row=0, loops="add")

@@ -223,7 +223,7 @@ class BatchNorm1d(nn.BatchNorm1d):
         if x.dim() != 2:
             raise ValueError("expected [num_nodes, num_features]")
         use_batch_stats = self.training or not self.track_running_stats
-        if not (use_batch_stats and x.is_cuda and x.size(0) > 1):
+        if not (use_batch_stats and x.is_cuda and x.size(0) > 1 and x.dtype != torch.bfloat16):   # bf16: torch
             y = super().forward(x)
             return torch.relu(y) if self.relu else y
         y, mean, _, var_u = torch.ops.mp.bn_act(x, self.weight, self.bias, float(self.eps), bool(self.relu))

@@ -23,12 +23,49 @@ def _f32c(t, name):
     return t if t.stride(-1) == 1 and t.dim() == 2 else t.contiguous()
 
 
+def _agg_in(t, name):
+    """an operand of the aggregation: float32, or bfloat16 (stored as bf16, aggregated in fp32); rows unit-stride"""
+    _require_hip(t, name)
+    if t.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"{name} must be float32 or bfloat16 (the path aggregates in fp32), got {t.dtype}")
+    return t if t.stride(-1) == 1 and t.dim() == 2 else t.contiguous()
+
+
+def _raw_spmm_bf16(g, x, reduce, S=None, self_scale=0.0, bias=None, relu=False, want_argmax=False, col_override=None,
+                   out=None):
+    """one launch of mp_spmm_csr_bf16: bf16 x, S and y, fp32 accumulation, bias passed as fp32; every output is that of
+    mp_spmm_csr_f32 on x.float() with the same plan, rounded once to bf16.  The tile kernels have no bf16 form."""
+    L = lib()
+    N, d = g.num_nodes, x.size(1)
+    y = out if out is not None else placement.empty_or_torch((N, d), x.device, reads=(x,), dtype=torch.bfloat16)
+    if S is not None and S.dtype != torch.bfloat16:
+        S = S.to(torch.bfloat16)
+    b = None if bias is None else bias.detach().to(torch.float32).contiguous()
+    argmax = torch.empty((N, d), dtype=torch.int32, device=x.device) if want_argmax else None
+    plan, counts = g.plan()
+    with torch.cuda.device(x.device):
+        nb = C.c_size_t(0)
+        check(L.mp_spmm_ws_bytes(counts, d, reduce, 0, C.byref(nb)))
+        ws = torch.empty(nb.value, dtype=torch.uint8, device=x.device) if nb.value else None
+        col = g.col if col_override is None else col_override
+        check(L.mp_spmm_csr_bf16(ptr(g.rowptr), ptr(col), ptr(g.val), N, ptr(plan), counts,
+                                 ptr(x), x.stride(0), ptr(y), y.stride(0), d, reduce,
+                                 ptr(S), S.stride(0) if S is not None else 0, float(self_scale),
+                                 ptr(b), _lib.ACT_RELU if relu else _lib.ACT_NONE, ptr(argmax),
+                                 ptr(ws), nb.value, _stream()), "mp_spmm_csr_bf16")
+    return y, argmax
+
+
 def _raw_spmm(g, x, reduce, S=None, self_scale=0.0, bias=None, relu=False, want_argmax=False,
               col_override=None, out=None):
     """one launch of mp_spmm_csr_f32 — or, for plain sum / mean / max (values only, no argmax) at d = 128 / 256 / 512 on
     a large operator, of mp_agg_rows_tiles_f32 (the same aggregation on the producer/consumer tile structure: 2-5 %
     faster; MP_AGG_TILES=0 keeps the plan-based kernel; for an X of >= AGG_HOT_MIN_BYTES its hot-column form,
-    mp_agg_rows_tiles_hot_f32: _hot_col) —; x [n_src, d] -> y [N, d] (written into `out` when given)"""
+    mp_agg_rows_tiles_hot_f32: _hot_col) —; x [n_src, d] -> y [N, d] (written into `out` when given).  A bf16 x goes
+    to mp_spmm_csr_bf16 (_raw_spmm_bf16)."""
+    if x.dtype == torch.bfloat16:
+        return _raw_spmm_bf16(g, x, reduce, S=S, self_scale=self_scale, bias=bias, relu=relu, want_argmax=want_argmax,
+                              col_override=col_override, out=out)
     L = lib()
     N, d = g.num_nodes, x.size(1)
     y = out if out is not None else placement.empty_or_torch((N, d), x.device, reads=(x,))
@@ -301,7 +338,10 @@ def _raw_dense_wgrad_relu(P, G, Y, want_bias=False, want_gm=True, gm_out=None):
 
 
 def _wgrad_and_bias(X, g, need_w, need_b):
-    """(X^T g, sum_m g[m]) for a transform's backward pass: one kernel when both are wanted"""
+    """(X^T g, sum_m g[m]) for a transform's backward pass: one kernel when both are wanted (bf16: library GEMM, the
+    column sums in fp32, cast)"""
+    if g.dtype == torch.bfloat16:
+        return (X.t() @ g if need_w else None), (g.float().sum(0).to(g.dtype) if need_b else None)
     if need_w and need_b:
         dW, db = _raw_dense_wgrad(X, g, want_bias=True)
         if dW is not None:
@@ -376,6 +416,11 @@ class _ConcatDense(torch.autograd.Function):
 
 
 def concat_dense(x, m, Ws, Wn, bias=None, relu=False):
+    if x.dtype == torch.bfloat16:     # no bf16 transform kernel: library ops
+        _require_hip(x, "x")
+        out = torch.cat([x @ Ws, m @ Wn], dim=1)
+        out = out if bias is None else out + bias
+        return torch.relu(out) if relu else out
     return _ConcatDense.apply(x, m, Ws, Wn, bias, bool(relu))
 
 
@@ -468,6 +513,9 @@ class _IndexAddRows(torch.autograd.Function):
 def index_add_rows(h, id_index, u):
     """out = h ; out[id[k]] += u[k]   (tensor_scatter_nd_add, TfgIDLayer.py:107,165,330,515;
     index_add_, idconv.py:67,155,251,310,375)"""
+    if h.dtype == torch.bfloat16:     # bf16: the library op
+        _require_hip(h, "h")
+        return h.index_add(0, id_index.to(torch.int64), u)
     return _IndexAddRows.apply(h, id_index, u)
 
 
@@ -499,6 +547,9 @@ class _GatherRows(torch.autograd.Function):
 
 def gather_rows(x, ids):
     """x[ids]  (tf.gather / index_select of the identity rows)"""
+    if x.dtype == torch.bfloat16:     # bf16: the library op
+        _require_hip(x, "x")
+        return x.index_select(0, ids.to(torch.int64))
     return _GatherRows.apply(x, ids)
 
 
@@ -748,10 +799,10 @@ def _empty_like_none(ref, dtype=torch.float32):
 def _op_spmm_raw(x: Tensor, graph: int, variant: int, reduce: int, S: Optional[Tensor], self_scale: float,
                  bias: Optional[Tensor], relu: bool, want_argmax: bool) -> Tuple[Tensor, Tensor]:
     g = from_handle(graph).variant(variant)
-    x = _f32c(x, "x")
+    x = _agg_in(x, "x")
     if x.size(0) != g.num_cols:
         raise ValueError(f"x has {x.size(0)} rows, the operator has {g.num_cols} columns")
-    Sc = None if S is None else _f32c(S, "S")
+    Sc = None if S is None else (_f32c(S, "S") if x.dtype == torch.float32 else _agg_in(S, "S"))
     y, argmax = _raw_spmm(g, x, reduce, S=Sc, self_scale=self_scale, bias=None if bias is None else bias.contiguous(),
                           relu=relu, want_argmax=want_argmax)
     return y, (argmax if argmax is not None else _empty_like_none(x, torch.int32))
@@ -761,7 +812,7 @@ def _op_spmm_raw(x: Tensor, graph: int, variant: int, reduce: int, S: Optional[T
 def _(x, graph, variant, reduce, S, self_scale, bias, relu, want_argmax):
     g = from_handle(graph)
     n = g.num_nodes if variant == 0 else g.num_cols
-    return (x.new_empty((n, x.size(1)), dtype=torch.float32),
+    return (x.new_empty((n, x.size(1))),
             x.new_empty((n, x.size(1)) if want_argmax else (0,), dtype=torch.int32))
 
 
@@ -769,13 +820,13 @@ def _(x, graph, variant, reduce, S, self_scale, bias, relu, want_argmax):
 def _op_spmm_rows_raw(x: Tensor, graph: int, variant: int, rows: Tensor) -> Tensor:
     """sum aggregation over the listed rows only of a graph variant: an [len(rows), n] operator"""
     sub = from_handle(graph).variant(variant).select_rows(rows)
-    y, _ = _raw_spmm(sub, _f32c(x, "x"), _lib.SUM)
+    y, _ = _raw_spmm(sub, _agg_in(x, "x"), _lib.SUM)
     return y
 
 
 @_op_spmm_rows_raw.register_fake
 def _(x, graph, variant, rows):
-    return x.new_empty((rows.numel(), x.size(1)), dtype=torch.float32)
+    return x.new_empty((rows.numel(), x.size(1)))
 
 
 @custom_op("mp::spmm_max_bwd_raw", mutates_args=(), device_types="cuda")
@@ -784,6 +835,11 @@ def _op_spmm_max_bwd_raw(dy: Tensor, argmax: Tensor, graph: int) -> Tensor:
     dy = dy.contiguous()
     N, d = dy.shape
     dx = torch.zeros((g.num_cols, d), dtype=torch.float32, device=dy.device)
+    if dy.dtype == torch.bfloat16:     # fp32 accumulation of the bf16 gradient, rounded once
+        with torch.cuda.device(dy.device):
+            check(lib().mp_spmm_max_bwd_bf16(ptr(g.col), ptr(g.val), ptr(argmax), ptr(dy), dy.stride(0), N, d, ptr(dx),
+                                             dx.stride(0), _stream()), "mp_spmm_max_bwd_bf16")
+        return dx.to(torch.bfloat16)
     with torch.cuda.device(dy.device):
         check(lib().mp_spmm_max_bwd_f32(ptr(g.col), ptr(g.val), ptr(argmax), ptr(dy), dy.stride(0), N, d, ptr(dx),
                                         dx.stride(0), _stream()), "mp_spmm_max_bwd_f32")
@@ -798,9 +854,22 @@ def _(dy, argmax, graph):
 @custom_op("mp::idgnn_agg_raw", mutates_args=(), device_types="cuda")
 def _op_idgnn_agg_raw(x: Tensor, graph: int, id_index: Tensor) -> Tuple[Tensor, Tensor]:
     g = from_handle(graph)
-    x = _f32c(x, "x")
+    x = _agg_in(x, "x")
     L = lib()
     N, d = g.num_nodes, x.size(1)
+    if x.dtype == torch.bfloat16:     # mp_idgnn_agg_bf16 (plan-based, fp32 accumulation); the tile kernels have no bf16 form
+        P = placement.empty_or_torch((N, d), x.device, reads=(x,), dtype=torch.bfloat16)
+        Q = placement.empty_or_torch((N, d), x.device, reads=(x,), dtype=torch.bfloat16)
+        col_marked = g.mark_ids(id_index)
+        plan, counts = g.plan()
+        with torch.cuda.device(x.device):
+            nb = C.c_size_t(0)
+            check(L.mp_spmm_ws_bytes(counts, d, _lib.SUM, 1, C.byref(nb)))
+            ws = torch.empty(nb.value, dtype=torch.uint8, device=x.device) if nb.value else None
+            check(L.mp_idgnn_agg_bf16(ptr(g.rowptr), ptr(col_marked), ptr(g.val), N, ptr(plan), counts,
+                                      ptr(x), x.stride(0), ptr(P), P.stride(0), ptr(Q), Q.stride(0), d,
+                                      ptr(ws), nb.value, _stream()), "mp_idgnn_agg_bf16")
+        return P, Q
     P = placement.empty_or_torch((N, d), x.device, reads=(x,))
     Q = placement.empty_or_torch((N, d), x.device, reads=(x,))
     if (d in AGG_TILES_WIDTHS and N >= AGG_TILES_MIN_ROWS and os.environ.get("MP_AGG_TILES", "1") != "0"
@@ -849,8 +918,8 @@ def _op_agg_dense_raw(x: Tensor, W: Tensor, bias: Optional[Tensor], graph: int, 
     """act((reduce_j w_ij x_j + s S_i) W + b): ONE launch where mp_agg_dense_f32 covers the operands, otherwise the
     aggregation kernel followed by the fused transform; returns (out, aggregated rows or an empty tensor)"""
     g = from_handle(graph).variant(variant)
-    x = _f32c(x, "x")
-    Sc = None if S is None else _f32c(S, "S")
+    x = _agg_in(x, "x")
+    Sc = None if S is None else (_f32c(S, "S") if x.dtype == torch.float32 else _agg_in(S, "S"))
     Wd = W.detach()
     if _agg_dense_kernel_ok(g, x, Wd, Sc):
         out, P = _raw_agg_dense(g, x, Wd, None if bias is None else bias.detach(), relu, S=Sc,
@@ -919,7 +988,16 @@ def _(gm, graph, id_index):
 
 
 def _dense_any(P, W, Q, W_id, bias, relu):
-    """act(P W [+ Q W_id] + b): the engine's MFMA kernel where it pays / applies, library GEMMs otherwise"""
+    """act(P W [+ Q W_id] + b): the engine's MFMA kernel where it pays / applies, library GEMMs otherwise (bf16: library
+    GEMMs, bias and ReLU)"""
+    if P.dtype == torch.bfloat16:
+        _require_hip(P, "P")
+        out = P @ W.to(P.dtype)
+        if Q is not None:
+            out = out + Q @ W_id.to(P.dtype)
+        if bias is not None:
+            out = out + bias.to(P.dtype)
+        return torch.relu(out) if relu else out
     Pc = _f32c(P, "P")
     Qc = None if Q is None else _f32c(Q, "Q")
     out = None
@@ -971,7 +1049,7 @@ def _op_dense_wgrad_relu_raw(X: Tensor, G: Tensor, Y: Tensor, want_b: bool,
     Gc = G if (G.stride(-1) == 1 and G.dim() == 2) else G.contiguous()
     Yc = Y if Y.stride(-1) == 1 else Y.contiguous()
     Xc = X if X.stride(-1) == 1 else X.contiguous()
-    r = _raw_dense_wgrad_relu(Xc, Gc, Yc, want_bias=want_b, want_gm=want_gm)
+    r = _raw_dense_wgrad_relu(Xc, Gc, Yc, want_bias=want_b, want_gm=want_gm) if Gc.dtype == torch.float32 else None
     if r is None:     # shape outside the kernel: separate passes
         gm = torch.ops.aten.threshold_backward(Gc, Yc, 0.0)
         dW, db = _wgrad_and_bias(Xc, gm, True, want_b)
@@ -1023,6 +1101,7 @@ def _spmm_setup(ctx, inputs, output):
     ctx.graph, ctx.reduce, ctx.self_scale, ctx.relu = graph, reduce, self_scale, relu
     ctx.g_alive = from_handle(graph)
     ctx.has_bias = bias is not None
+    ctx.bias_dtype = None if bias is None else bias.dtype
     ctx.save_for_backward(y if relu else None, argmax)
 
 
@@ -1033,7 +1112,9 @@ def _spmm_backward(ctx, dy, _dargmax):
     dy = dy.contiguous()
     if ctx.relu:
         dy = torch.ops.aten.threshold_backward(dy, y, 0.0)    # one vectorised pass
-    dbias = dy.sum(0) if (ctx.has_bias and ctx.needs_input_grad[4]) else None
+    dbias = None
+    if ctx.has_bias and ctx.needs_input_grad[4]:
+        dbias = dy.sum(0) if dy.dtype == torch.float32 else dy.float().sum(0).to(ctx.bias_dtype)   # bf16: summed in fp32
     dx = None
     if ctx.needs_input_grad[0]:
         S = dy if ctx.self_scale != 0.0 else None

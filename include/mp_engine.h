@@ -263,6 +263,35 @@ int mp_spmm_max_bwd_f32(const int32_t* col, const float* val, const int32_t* arg
                         float* dX, int64_t ldx, mp_stream_t stream);
 
 /* ------------------------------------------------------------------ *
+ * bf16 storage, fp32 accumulation                     *
+ * ------------------------------------------------------------------ */
+/*
+ * The contract of mp_spmm_csr_f32 with X, S and Y as bf16 (element strides ldx, lds, ldy); val and bias stay fp32.
+ * Rows are widened to fp32 as they are read (exact) and reduced, averaged and run through the epilogue in fp32 in the
+ * fp32 kernel's order (entry order within a row, hub pieces in piece order); every output element is rounded once to
+ * bf16, to nearest even.  So Y is bit for bit mp_spmm_csr_f32 on the widened X (and S) with the same plan, rounded to
+ * bf16, and argmax is bit for bit its argmax.  Any d >= 1, ldx >= d; the workspace is mp_spmm_ws_bytes' (fp32
+ * partials).  N >= 2^31: MP_ERR_UNSUPPORTED.
+ */
+int mp_spmm_csr_bf16(const int32_t* rowptr, const int32_t* col, const float* val,
+                     int64_t N, const int32_t* plan, const int32_t* counts_host,
+                     const void* X, int64_t ldx, void* Y, int64_t ldy, int32_t d,
+                     int reduce, const void* S, int64_t lds, float self_scale,
+                     const float* bias, int act, int32_t* argmax,
+                     void* ws, size_t ws_bytes, mp_stream_t stream);
+/* mp_idgnn_agg_f32 with X, P and Q as bf16: P and Q are that kernel's fp32 rows on the widened X, rounded once */
+int mp_idgnn_agg_bf16(const int32_t* rowptr, const int32_t* col_marked, const float* val,
+                      int64_t N, const int32_t* plan, const int32_t* counts_host,
+                      const void* X, int64_t ldx, void* P, int64_t ldp,
+                      void* Q, int64_t ldq, int32_t d,
+                      void* ws, size_t ws_bytes, mp_stream_t stream);
+/* mp_spmm_max_bwd_f32 with a bf16 dY: dX (fp32, zeroed by the caller) accumulates the widened gradients; the caller
+ * rounds it once */
+int mp_spmm_max_bwd_bf16(const int32_t* col, const float* val, const int32_t* argmax,
+                         const void* dY, int64_t ldy, int64_t N, int32_t d,
+                         float* dX, int64_t ldx, mp_stream_t stream);
+
+/* ------------------------------------------------------------------ *
  * BatchNorm1d over the node axis in training mode with the activation  *
  * fused (K20 / SURVEY §8f rank 3): graphgym/models/layer.py:26-35,      *
  * keras BatchNormalization of main_zd.py:181-186.                       *
