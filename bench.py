@@ -4,6 +4,7 @@ GCN d=256 on 100M-edge scale-free").
 
     python bench.py --gpus 1 --steps 50 --warmup 20
     python bench.py --gpus 1 --steps 50 --warmup 20 --dump-outputs DIR   # + a fixed sample of the last step's Y as DIR/*.npy
+    python bench.py --gpus 1 --steps 50 --warmup 20 --full  # + the side measurements (below)
     python bench.py --gpus N --steps K --warmup W          # no launcher: bench.py starts its N ranks itself
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W [--mode step]
@@ -22,15 +23,24 @@ entries incl. self loops), X [10^7, 256] fp32.  With N > 1 every rank owns its o
 over RCCL, Adam) on each rank's shard of a batch of ego nets dealt out by stored entries (LPT); the
 all-reduce is inside the timed region and also reported on its own (`allreduce_ms`).
 
-Prints ONE JSON line on rank 0.  `roofline` prices the aggregation launch against HBM; `cpu_baseline`
-times the CPU oracle (the op-for-op restatement of the reference's CPU path) on a bounded sample of the
-same workload on this box's host cores.
+Prints ONE JSON line on rank 0.  `roofline` prices the timed launches against HBM.
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line: nothing else.  --full adds,
+after the timed steps and never part of `value`, the measurements that take launches or CPU time of their own:
+  roofline.launch_ms_cold_median      launches after a 512 MB memset that flushes L2 / Infinity Cache
+  roofline.stream_*_gbps_measured     a read-only pass over X and a copy X -> Y (and frac_of_measured_read_stream)
+  output_placement.unchecked_ms,      the same launch with Y as torch hands it out unchecked, and with the best of
+    best_of_8_ms                      8 checked candidates (one GPU)
+  backward                            dX = A_hat^T dY on the transposed CSR (one GPU)
+  layer                               relu((A_hat X) W + b) as one kernel next to two (one GPU)
+  cpu_baseline                        the CPU oracle (the op-for-op restatement of the reference's CPU path) on a
+                                      bounded sample of the same workload on the host's cores (one GPU; not with
+                                      --no-cpu-baseline)
 
 X is a plain torch tensor (what a GraphGym first layer is handed).  Y is allocated ONCE by the very call the product's
 operators make for their outputs (graphgym_amd.placement.empty_or_torch(reads=(X,)): a torch allocation, a timed-copy
 check against X, re-allocation on conflict — at most MP_PLACE_TRIES candidates); `value` and `roofline` are measured on
-that Y.  Side fields, never part of `value`: the same launch with Y as torch hands it out unchecked
-(`output_placement.unchecked_ms`) and with the best of 8 candidates (`output_placement.best_of_8_ms`).
+that Y.
 """
 import argparse
 import json
@@ -223,36 +233,39 @@ def run_aggregate(args, rank, world, dev):
     def pct(p):
         return per_step[min(len(per_step) - 1, int(round(p * (len(per_step) - 1))))]
 
-    # cold launches: a 512 MB memset between launches flushes L2 / Infinity Cache
-    flush = torch.empty(512 << 20, dtype=torch.uint8, device=dev)
-    cold = []
-    for _ in range(min(10, args.steps)):
-        flush.zero_()
-        a0, a1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a0.record()
-        step()
-        a1.record()
-        torch.cuda.synchronize()
-        cold.append(a0.elapsed_time(a1))
-    cold.sort()
-    del flush
+    # the side measurements below run with --full only: after the timed region, never part of `value`, each with
+    # launches or CPU time of its own
+    if args.full:
+        # cold launches: a 512 MB memset between launches flushes L2 / Infinity Cache
+        flush = torch.empty(512 << 20, dtype=torch.uint8, device=dev)
+        cold = []
+        for _ in range(min(10, args.steps)):
+            flush.zero_()
+            a0, a1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a0.record()
+            step()
+            a1.record()
+            torch.cuda.synchronize()
+            cold.append(a0.elapsed_time(a1))
+        cold.sort()
+        del flush
 
-    # measured streaming rates on this box: a read-only pass over X (the aggregation is 92 % reads) and a
-    # copy X -> Y (50 % writes); the aggregation's algorithmic rate is quoted against both and the nominal peak
-    from graphgym_amd._lib import lib as _mplib, ptr as _ptr, check as _check
-    from graphgym_amd.graph import _stream as _mpstream
-    sink = torch.empty(256 * 8 * 256, dtype=torch.float32, device=dev)
-    read_ms = _ms(lambda: _check(_mplib().mp_read_probe_f32(_ptr(x), x.numel(), _ptr(sink), _mpstream())))
-    copy_ms = _ms(lambda: _check(_mplib().mp_copy_probe_f32(_ptr(x), _ptr(y), x.numel(), _mpstream())))
-    read_gbps = x.numel() * 4 / (read_ms * 1e-3) / 1e9
-    copy_gbps = 2 * x.numel() * 4 / (copy_ms * 1e-3) / 1e9
+        # measured streaming rates: a read-only pass over X (the aggregation is 92 % reads) and a copy X -> Y
+        # (50 % writes); the aggregation's algorithmic rate is quoted against both and the nominal peak
+        from graphgym_amd._lib import lib as _mplib, ptr as _ptr, check as _check
+        from graphgym_amd.graph import _stream as _mpstream
+        sink = torch.empty(256 * 8 * 256, dtype=torch.float32, device=dev)
+        read_ms = _ms(lambda: _check(_mplib().mp_read_probe_f32(_ptr(x), x.numel(), _ptr(sink), _mpstream())))
+        copy_ms = _ms(lambda: _check(_mplib().mp_copy_probe_f32(_ptr(x), _ptr(y), x.numel(), _mpstream())))
+        read_gbps = x.numel() * 4 / (read_ms * 1e-3) / 1e9
+        copy_gbps = 2 * x.numel() * 4 / (copy_ms * 1e-3) / 1e9
 
     balg = algorithmic_bytes(n, g.nnz, d, g.val is not None)
     balg_total = D.all_reduce_sum(balg, dev)
 
     # side legs (after the timed region, never part of `value`): the same launch into a buffer exactly as torch hands it
     # out, unchecked, and into the best of 8 checked candidates
-    if world == 1 and placement.enabled():
+    if args.full and world == 1 and placement.enabled():
         try:
             y_plain = torch.empty((n, d), dtype=torch.float32, device=dev)
             place["unchecked_ms"] = time_into(y_plain)
@@ -266,7 +279,7 @@ def run_aggregate(args, rank, world, dev):
 
     # backward of the aggregation = the same kernel on the transposed operator (dX = A_hat^T dY)
     backward = None
-    if world == 1:
+    if args.full and world == 1:
         try:
             gt = g.transpose()
             gt.plan()
@@ -282,7 +295,7 @@ def run_aggregate(args, rank, world, dev):
     # the whole layer (aggregate, then the MFMA feature transform + bias + ReLU) as ONE kernel next to the
     # two-kernel order: reported beside the metric, never part of `value`
     layer = None
-    if world == 1 and d in ops.FUSED_WIDTHS:
+    if args.full and world == 1 and d in ops.FUSED_WIDTHS:
         try:
             Wl = (torch.rand((d, d), device=dev, generator=gen) - 0.5) * (2.0 / d ** 0.5)
             bl = torch.rand((d,), device=dev, generator=gen) - 0.5
@@ -338,20 +351,22 @@ def run_aggregate(args, rank, world, dev):
             "hbm_gbps_algorithmic": achieved,
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
-                         "stream_read_gbps_measured": read_gbps, "stream_copy_gbps_measured": copy_gbps,
-                         "frac_of_measured_read_stream": achieved / read_gbps,
                          "algorithmic_bytes_per_launch": balg, "launch_ms": launch_ms,
                          "launch_ms_min_median_max": [per_step[0], per_step[len(per_step) // 2], per_step[-1]],
                          "launch_ms_p10_p90": [pct(0.1), pct(0.9)],
-                         "launch_ms_cold_median": cold[len(cold) // 2] if cold else None,
-                         "cold_note": "512 MB memset between launches (L2 / Infinity Cache flushed)",
                          "kernel": kernel_label},
         }
+        if args.full:
+            res["roofline"].update({
+                "stream_read_gbps_measured": read_gbps, "stream_copy_gbps_measured": copy_gbps,
+                "frac_of_measured_read_stream": achieved / read_gbps,
+                "launch_ms_cold_median": cold[len(cold) // 2] if cold else None,
+                "cold_note": "512 MB memset between launches (L2 / Infinity Cache flushed)"})
         if backward is not None:
             res["backward"] = backward
         if layer is not None:
             res["layer"] = layer
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(g, x)
         if world > 1:
             # the whole job against the whole job's roof: N independent HBM systems
@@ -436,7 +451,10 @@ def main():
     ap.add_argument("--graph", choices=["ba", "powerlaw_cluster"], default="ba",
                     help="ba = Barabasi-Albert (default); powerlaw_cluster = Holme-Kim with triangle probability 0.3")
     ap.add_argument("--permute", action="store_true", help="relabel nodes by a random permutation (seed 1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the side measurements: cold launches, stream probes, output "
+                         "placement legs, backward, the one-kernel layer and the CPU baseline (module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--centres", type=int, default=4096, help="step: ego-net centres per GPU in the global batch")
     ap.add_argument("--step-model", choices=["idgcn", "idgin"], default="idgcn")
     ap.add_argument("--step-nodes", type=int, default=2_000_000, help="step: nodes of the base graph the ego nets are cut from")

@@ -1,5 +1,6 @@
-"""bench.py keeps its contract: one JSON line with the driver's keys, the roofline and cpu_baseline objects,
-and the same under a 2-rank launch (ranks share the box's GPU, gloo for the scalar reductions)."""
+"""bench.py keeps its contract: one JSON line with the driver's keys and the roofline object; a plain run stops there,
+--full adds the side measurements and the cpu_baseline object; and the same under a 2-rank launch (ranks share the
+box's GPU, gloo for the scalar reductions)."""
 import json
 import os
 import socket
@@ -12,6 +13,11 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
         "vs_baseline", "dtype", "data", "config", "roofline"}
+# what only --full measures (after the timed steps, each with launches or CPU time of its own)
+FULL_KEYS = {"cpu_baseline", "backward", "layer"}
+FULL_ROOFLINE_KEYS = {"stream_read_gbps_measured", "stream_copy_gbps_measured", "frac_of_measured_read_stream",
+                      "launch_ms_cold_median", "cold_note"}
+FULL_PLACEMENT_KEYS = {"unchecked_ms", "best_of_8_ms", "best_of_8_candidates_ms", "side_legs_error"}
 
 
 def _last_json(out):
@@ -20,12 +26,7 @@ def _last_json(out):
     return json.loads(lines[0])
 
 
-def test_single_gpu_line(dev):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--nodes", "300000", "--steps", "4",
-                        "--warmup", "2"], capture_output=True, text=True, timeout=600, cwd=ROOT)
-    assert r.returncode == 0, r.stderr[-2000:]
-    d = _last_json(r.stdout)
-    assert KEYS <= set(d) and "cpu_baseline" in d
+def _check_single_gpu_line(d):
     assert d["n_gpus"] == 1 and d["steps"] == 4 and d["warmup"] == 2 and d["scaling"] == "weak"
     assert d["unit"] == "edges/s" and d["dtype"] == "f32" and d["vs_baseline"] is None and d["higher_is_better"] is True
     assert "workload" in d["config"] and "model" not in d["config"]
@@ -34,6 +35,28 @@ def test_single_gpu_line(dev):
     assert abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-9
     nnz = d["config"]["stored_entries_per_gpu"]
     assert abs(d["value"] - nnz / (d["ms_per_step"] * 1e-3)) <= 0.02 * d["value"]     # value = units / time
+
+
+def test_plain_single_gpu_line_is_lean(dev):
+    """without --full: the headline line alone, none of the side measurements"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--nodes", "300000", "--steps", "4",
+                        "--warmup", "2"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _last_json(r.stdout)
+    assert KEYS <= set(d) and not FULL_KEYS & set(d)
+    assert not FULL_ROOFLINE_KEYS & set(d["roofline"])
+    assert not FULL_PLACEMENT_KEYS & set(d["config"]["output_placement"])
+    _check_single_gpu_line(d)
+
+
+def test_single_gpu_line(dev):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--nodes", "300000", "--steps", "4",
+                        "--warmup", "2", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _last_json(r.stdout)
+    assert KEYS <= set(d) and FULL_KEYS <= set(d)
+    assert FULL_ROOFLINE_KEYS <= set(d["roofline"])
+    _check_single_gpu_line(d)
     cb = d["cpu_baseline"]
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0 and "sample" in cb
 
