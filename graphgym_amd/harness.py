@@ -270,7 +270,42 @@ class GNNGraphHead(nn.Module):
         return batch.graph_feature, batch.graph_label
 
 
-head_dict = {'node': GNNNodeHead, 'graph': GNNGraphHead}     # head.py:122-127 ('edge' / 'link_pred' are off the path)
+class GNNEdgeHead(nn.Module):
+    """graphgym/models/head.py:40-85: decode the label pairs batch.edge_label_index [2, K] from the node embeddings.
+    cfg.model.edge_decoding 'concat': MLP(2 dim_in, dim_out) on cat(h[a], h[b]); 'dot' / 'cosine_similarity': MLP(dim_in,
+    dim_in) over the batch, then the pair's dot product / cosine similarity (binary only: dim_out > 1 raises).
+    transform: edge batches (edge_nets.edge_batch) are node classification and train through GNNNodeHead instead."""
+
+    def __init__(self, dim_in, dim_out):
+        super().__init__()
+        self.decoding = getattr(cfg.model, "edge_decoding", "dot")
+        if self.decoding == 'concat':
+            self.layer_post_mp = MLP(dim_in * 2, dim_out, num_layers=cfg.gnn.layers_post_mp, bias=True)
+            return
+        if dim_out > 1:
+            raise ValueError('Binary edge decoding ({}) is used for multi-class edge/link prediction.'.format(
+                self.decoding))
+        if self.decoding not in ('dot', 'cosine_similarity'):
+            raise ValueError('Unknown edge decoding {}.'.format(self.decoding))
+        self.layer_post_mp = MLP(dim_in, dim_in, num_layers=cfg.gnn.layers_post_mp, bias=True)
+
+    def _apply_index(self, batch):
+        return batch.node_feature[batch.edge_label_index], batch.edge_label
+
+    def forward(self, batch):
+        if self.decoding != 'concat':
+            batch = self.layer_post_mp(batch)
+        pred, label = self._apply_index(batch)
+        a, b = pred[0], pred[1]
+        if self.decoding == 'concat':
+            return self.layer_post_mp(torch.cat((a, b), dim=-1)), label
+        if self.decoding == 'dot':
+            return (a * b).sum(dim=-1), label
+        return F.cosine_similarity(a, b, dim=-1), label
+
+
+head_dict = {'node': GNNNodeHead, 'graph': GNNGraphHead,      # head.py:122-127
+             'edge': GNNEdgeHead, 'link_pred': GNNEdgeHead}
 
 
 class GNN(nn.Module):

@@ -579,6 +579,49 @@ int mp_ego_expand(const int32_t* rowptr, const int32_t* col, int64_t N,
                   mp_ego_result_t* out, mp_stream_t stream);
 
 /* ------------------------------------------------------------------ *
+ * Edge-net batches (graphgym/models/transform.py:41-65) on the device. *
+ * The base CSR (engine convention: row = destination, columns         *
+ * ascending inside a row) is the disjoint union of n_graphs graphs,   *
+ * graph g = nodes graph_ptr[g] .. graph_ptr[g+1] (device, int64).     *
+ * Copy c (device tables) is a relabelled copy of graph copy_graph[c]  *
+ * whose identity node is its local node copy_src[c]: node j of copy c *
+ * gets the new id node_base[c] + j.  node_base / entry_base [C+1] are *
+ * the caller's prefix sums of the copies' nodes and stored entries    *
+ * (N' = node_base[C], E' = entry_base[C]); max_graph_size bounds the  *
+ * nodes and the entries of any copied graph.  Every output is          *
+ * preallocated and written once:                                       *
+ *   edge_index [2, E'] int64: row 0 sources, row 1 destinations (PyG), *
+ *     listed in the engine's CSR order (dst, src in the new ids);      *
+ *   orig_node [N'] base node, copy_of_node [N'] int32,                 *
+ *   orig_edge [E'] eid[base entry] (the entry's position in the base's *
+ *     edge_index), or the base entry itself where eid is NULL;         *
+ *   id_index [C] node_base[c] + copy_src[c];                           *
+ *   flags MP_EGO_CSR (| MP_EGO_CSR_SELF_LOOPS): csr_rowptr [N'+1],      *
+ *     csr_col / csr_eid [E' (+ N')] as mp_csr_from_coo builds them from *
+ *     edge_index (an inserted self entry: eid = -1 - row).              *
+ * `row` is the base's row of every stored entry (mp_csr_row_ids).      *
+ * N' or E' (+ N') beyond int32: MP_ERR_UNSUPPORTED.  No synchronisation.*
+ * ------------------------------------------------------------------ */
+int mp_edge_expand(const int32_t* rowptr, const int32_t* col, const int32_t* row, const int32_t* eid,
+                   int64_t N, int64_t nnz, const int64_t* graph_ptr, int64_t n_graphs,
+                   const int32_t* copy_graph, const int32_t* copy_src, const int64_t* node_base,
+                   const int64_t* entry_base, int64_t n_copies, int64_t n_out_nodes, int64_t n_out_edges,
+                   int64_t max_graph_size, int32_t flags, int64_t* edge_index, int64_t* orig_node,
+                   int32_t* copy_of_node, int64_t* orig_edge, int64_t* id_index, int32_t* csr_rowptr,
+                   int32_t* csr_col, int32_t* csr_eid, mp_stream_t stream);
+/* Hop distances (transform.py:68-90's nx shortest path lengths): dist[pair_pos[p]] = the number of hops of the shortest
+ * path from sources[s] to pair_dst[p] (p in pair_off[s] .. pair_off[s+1], pairs grouped by source) along the rows of the
+ * CSR (row u = the nodes u reaches in one hop: pass the transpose of a directed engine CSR), inside the source's graph
+ * source_graph[s]; 0 for the source itself, -1 if unreachable or in another graph.  Exact at any depth.  One workgroup
+ * per distinct source with its bitmaps in LDS: max_graph_nodes (largest graph that holds a source) above 65536 is
+ * MP_ERR_UNSUPPORTED.  No synchronisation. */
+int mp_hop_distances(const int32_t* rowptr, const int32_t* col, int64_t N, int64_t nnz,
+                     const int64_t* graph_ptr, int64_t n_graphs, int64_t max_graph_nodes,
+                     const int64_t* sources, const int32_t* source_graph, int64_t n_sources,
+                     const int64_t* pair_off, const int64_t* pair_dst, const int64_t* pair_pos,
+                     int64_t n_pairs, int32_t* dist, mp_stream_t stream);
+
+/* ------------------------------------------------------------------ *
  * Host-side sharding of independent units over ranks (not a device op) *
  * graphgym/loader.py:247-251 (a batch is a disjoint union of graphs),  *
  * graphgym/models/transform.py:24-36 (ego nets are disjoint): units by  *
