@@ -17,23 +17,72 @@
 //     bitwise reproducible;
 //   * rows longer than hub_deg are cut into pieces that separate waves reduce
 //     into a small partial buffer, summed in piece order by a finalize kernel.
+//
+// One body serves two stored element types, chosen by the traits E: F32, and Bf16, where X, S, Y and
+// Q are stored as bf16 and every reduction and epilogue step runs in fp32.  A gathered bf16 row is kept as packed
+// words until it is used and then widened (a 16-bit shift, exact), so the terms, their order and every fp32 operation
+// on them are those of the F32 kernel on the widened X: each bf16 output is that kernel's fp32 value rounded once
+// (round to nearest even, v_cvt_pk_bf16_f32).  A lane reads W bf16 (2W bytes, up to 16 B); a 512-byte row (d = 256,
+// W = 4) is half the bytes of the fp32 1 KiB row per load instruction, so Bf16 keeps twice the rows in flight per
+// wave below W = 8.  The partials of the hub path are fp32 for both.
 #include "common.h"
 #include "vecio.h"
 #include <limits.h>
 
 namespace mp {
 
+// The stored element of X, S, Y and Q: how a gathered row is loaded (Raw: its per-lane register form) and widened to
+// fp32, how S is loaded, a row stored and one element of dY widened (max backward), the widest lane vector and the
+// rows in flight U per wave.
+struct F32 {
+  using T = float;
+  template <int W> using Raw = float[W];
+  static constexpr int kMaxW = 4;
+  template <int W> static constexpr int kU = 8;
+  static constexpr bool kExtras = true;      // the col_scale / L2 epilogue and multi-head weights
+  static constexpr bool kNtFinalize = true;  // the hub finalize stores Y non-temporally
+  template <int W> static __device__ __forceinline__ void load_raw(const T* p, Raw<W>& r) { load_vec<W>(p, r); }
+  template <int W> static __device__ __forceinline__ void widen(const Raw<W>& r, float (&v)[W]) {
+#pragma unroll
+    for (int k = 0; k < W; ++k) v[k] = r[k];
+  }
+  template <int W> static __device__ __forceinline__ void load(const T* p, float (&v)[W]) { load_vec<W>(p, v); }
+  static __device__ __forceinline__ float to_f32(T x) { return x; }
+  template <int W, bool NT> static __device__ __forceinline__ void store(T* p, const float (&v)[W]) {
+    if constexpr (NT) store_vec_nt<W>(p, v);
+    else store_vec<W>(p, v);
+  }
+};
+
+struct Bf16 {
+  using T = uint16_t;
+  template <int W> using Raw = uint32_t[bf16_words<W>()];
+  static constexpr int kMaxW = 8;
+  template <int W> static constexpr int kU = W == 8 ? 8 : 16;  // the same bytes outstanding per lane (128) at W = 8, 4
+  static constexpr bool kExtras = false;
+  static constexpr bool kNtFinalize = false;
+  template <int W> static __device__ __forceinline__ void load_raw(const T* p, Raw<W>& r) { load_bf16_raw<W>(p, r); }
+  template <int W> static __device__ __forceinline__ void widen(const Raw<W>& r, float (&v)[W]) { widen_bf16<W>(r, v); }
+  template <int W> static __device__ __forceinline__ void load(const T* p, float (&v)[W]) { load_bf16<W>(p, v); }
+  static __device__ __forceinline__ float to_f32(T x) { return __builtin_bit_cast(float, (uint32_t)x << 16); }
+  template <int W, bool NT> static __device__ __forceinline__ void store(T* p, const float (&v)[W]) {
+    store_bf16<W, NT>(p, v);
+  }
+};
+
+template <class E>
 struct AggArgs {
+  using T = typename E::T;
   const int32_t* rowptr;
   const int32_t* col;
   const float* val;
   const int32_t* seg_row;
   int32_t n_seg;
   int32_t hub_deg;
-  const float* X; int64_t ldx;
-  float* Y; int64_t ldy;
-  float* Q; int64_t ldq;
-  const float* S; int64_t lds; float self_scale;
+  const T* X; int64_t ldx;
+  T* Y; int64_t ldy;
+  T* Q; int64_t ldq;
+  const T* S; int64_t lds; float self_scale;
   const float* bias;
   const float* col_scale;   // per-column multiplier applied before bias (BatchNorm in eval mode folded)
   int32_t act;
@@ -56,7 +105,7 @@ struct AggArgs {
 };
 
 // Running reduction of one output row, W columns per lane.
-template <int W, int REDUCE, bool BRANCH2>
+template <class E, int W, int REDUCE, bool BRANCH2>
 struct RowAcc {
   float a[W];
   float b[BRANCH2 ? W : 1];
@@ -70,8 +119,10 @@ struct RowAcc {
       if constexpr (REDUCE == MP_MAX) arg[k] = -1;
     }
   }
-  // one neighbour row v scaled by w; `marked`: source is an identity node; e: entry index
-  __device__ __forceinline__ void add(const float (&v)[W], float w, bool marked, int e) {
+  // one neighbour row r (raw, widened here) scaled by w; `marked`: source is an identity node; e: entry index
+  __device__ __forceinline__ void add(const typename E::template Raw<W>& r, float w, bool marked, int e) {
+    float v[W];
+    E::template widen<W>(r, v);
 #pragma unroll
     for (int k = 0; k < W; ++k) {
       if constexpr (REDUCE == MP_MAX) {
@@ -91,9 +142,9 @@ struct RowAcc {
 };
 
 // Epilogue + store of one finished output row (K15/K17 fused into the flush).
-template <int W, int REDUCE, bool BRANCH2, bool NT = true>
-__device__ __forceinline__ void finish_row(const AggArgs& a, int row, int deg,
-                                           RowAcc<W, REDUCE, BRANCH2>& acc,
+template <class E, int W, int REDUCE, bool BRANCH2, bool NT>
+__device__ __forceinline__ void finish_row(const AggArgs<E>& a, int row, int deg,
+                                           RowAcc<E, W, REDUCE, BRANCH2>& acc,
                                            int c0, int c0ld, bool lane_on) {
   float out[W];
 #pragma unroll
@@ -104,19 +155,19 @@ __device__ __forceinline__ void finish_row(const AggArgs& a, int row, int deg,
   }
   if (a.S != nullptr) {
     float s[W];
-    load_vec<W>(a.S + (int64_t)row * a.lds + c0ld, s);
+    E::template load<W>(a.S + (int64_t)row * a.lds + c0ld, s);
 #pragma unroll
     for (int k = 0; k < W; ++k) out[k] = fmaf(a.self_scale, s[k], out[k]);
   }
-  if (a.col_scale != nullptr) {
+  if (E::kExtras && a.col_scale != nullptr) {
     float sv[W];
-    load_vec<W>(a.col_scale + c0ld, sv);
+    load_f32<W>(a.col_scale + c0ld, sv);
 #pragma unroll
     for (int k = 0; k < W; ++k) out[k] *= sv[k];
   }
   if (a.bias != nullptr) {
     float bv[W];
-    load_vec<W>(a.bias + c0ld, bv);
+    load_f32<W>(a.bias + c0ld, bv);
 #pragma unroll
     for (int k = 0; k < W; ++k) out[k] += bv[k];
   }
@@ -124,7 +175,7 @@ __device__ __forceinline__ void finish_row(const AggArgs& a, int row, int deg,
 #pragma unroll
     for (int k = 0; k < W; ++k) out[k] = fmaxf(out[k], 0.f);
   }
-  if (a.l2norm) {
+  if (E::kExtras && a.l2norm) {
     // F.normalize(p=2, dim=-1) (layer.py:43-46, gnn.py:79-80): the wave holds the whole row
     float ss = 0.f;
     if (lane_on) {
@@ -137,23 +188,22 @@ __device__ __forceinline__ void finish_row(const AggArgs& a, int row, int deg,
     for (int k = 0; k < W; ++k) out[k] *= inv;
   }
   if (lane_on) {
-    if constexpr (NT) store_vec_nt<W>(a.Y + (int64_t)row * a.ldy + c0, out);
-    else store_vec<W>(a.Y + (int64_t)row * a.ldy + c0, out);
-    if constexpr (BRANCH2) store_vec<W>(a.Q + (int64_t)row * a.ldq + c0, acc.b);
+    E::template store<W, NT>(a.Y + (int64_t)row * a.ldy + c0, out);
+    if constexpr (BRANCH2) E::template store<W, false>(a.Q + (int64_t)row * a.ldq + c0, acc.b);
     if constexpr (REDUCE == MP_MAX) {
-      if (a.argmax != nullptr) store_ivec<W>(a.argmax + (int64_t)row * a.d + c0, acc.arg);
+      if (a.argmax != nullptr) store_i32<W>(a.argmax + (int64_t)row * a.d + c0, acc.arg);
     }
   }
   acc.reset();
 }
 
 // Main kernel: one wave per segment of whole rows.  Kept from the round-1 variant study: U = 8 rows
-// in flight, non-temporal stores of Y (-1.2 %); non-temporal index loads, index prefetch and an LDS-staged index
-// tile measured within 0.3 % and are not built.
+// in flight (fp32; Bf16::kU for bf16), non-temporal stores of Y (-1.2 %); non-temporal index loads, index prefetch
+// and an LDS-staged index tile measured within 0.3 % and are not built.
 // NH > 1 (multi-head attention, TfgIDLayer.py:333-355): every entry carries NH weights (val [nnz, NH]); a lane applies
 // the weight of the head its columns belong to, so all heads aggregate in one launch on full 1 KiB row loads.
-template <int W, int REDUCE, bool WEIGHTED, bool BRANCH2, int U, int NH = 1>
-__global__ __launch_bounds__(kBlock) void agg_rows_kernel(AggArgs a) {
+template <class E, int W, int REDUCE, bool WEIGHTED, bool BRANCH2, int U, int NH = 1>
+__global__ __launch_bounds__(kBlock) void agg_rows_kernel(AggArgs<E> a) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int seg = blockIdx.x * kWavesPerBlock + wave;
@@ -174,7 +224,7 @@ __global__ __launch_bounds__(kBlock) void agg_rows_kernel(AggArgs a) {
   }
   if (r0 >= r1) return;
 
-  const float* __restrict__ xlane = a.X + c0ld;
+  const typename E::T* __restrict__ xlane = a.X + c0ld;
   const int myh = NH > 1 ? c0ld / a.head_width : 0;
 
   // row ends of up to 64 rows live in one VGPR; the current one is broadcast to an SGPR
@@ -184,7 +234,7 @@ __global__ __launch_bounds__(kBlock) void agg_rows_kernel(AggArgs a) {
   int rstart = e0;
   int rend = bcast_i(rendv, 0);
 
-  RowAcc<W, REDUCE, BRANCH2> acc;
+  RowAcc<E, W, REDUCE, BRANCH2> acc;
   acc.reset();
 
   auto advance = [&]() {
@@ -205,20 +255,20 @@ __global__ __launch_bounds__(kBlock) void agg_rows_kernel(AggArgs a) {
     for (int h = 0; h < NH; ++h) wv[h] = WEIGHTED ? a.val[(int64_t)me * NH + h] : 1.f;
     const int n = min(kWave, e1 - ec);
     for (int jb = 0; jb < n; jb += U) {
-      float v[U][W];
+      typename E::template Raw<W> v[U];
       int cj[U];
 #pragma unroll
       for (int j = 0; j < U; ++j) {
         cj[j] = bcast_i(cv, jb + j);
         const int c = BRANCH2 ? (cj[j] & 0x7fffffff) : cj[j];
-        load_vec<W>(xlane + (int64_t)c * a.ldx, v[j]);
+        E::template load_raw<W>(xlane + (int64_t)c * a.ldx, v[j]);
       }
 #pragma unroll
       for (int j = 0; j < U; ++j) {
         const int e = ec + jb + j;
         if (e < e1) {
           while (e >= rend) {
-            finish_row<W, REDUCE, BRANCH2, true>(a, r, rend - rstart, acc, c0, c0ld, lane_on);
+            finish_row<E, W, REDUCE, BRANCH2, true>(a, r, rend - rstart, acc, c0, c0ld, lane_on);
             advance();
           }
           float w = WEIGHTED ? bcast_f(wv[0], jb + j) : 1.f;
@@ -233,20 +283,20 @@ __global__ __launch_bounds__(kBlock) void agg_rows_kernel(AggArgs a) {
     }
   }
   while (r < r1) {
-    finish_row<W, REDUCE, BRANCH2, true>(a, r, rend - rstart, acc, c0, c0ld, lane_on);
+    finish_row<E, W, REDUCE, BRANCH2, true>(a, r, rend - rstart, acc, c0, c0ld, lane_on);
     advance();
   }
 }
 
 // Hub path 1/2: one wave reduces one piece (<= piece_edges entries) of a hub row.
-template <int W, int REDUCE, bool WEIGHTED, bool BRANCH2, int U, int NH = 1>
-__global__ __launch_bounds__(kBlock) void agg_hub_pieces_kernel(AggArgs a) {
+template <class E, int W, int REDUCE, bool WEIGHTED, bool BRANCH2, int U, int NH = 1>
+__global__ __launch_bounds__(kBlock) void agg_hub_pieces_kernel(AggArgs<E> a) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int c0 = (blockIdx.y * kWave + lane) * W;
   const bool lane_on = c0 < a.d;
   const int c0ld = lane_on ? c0 : 0;
-  const float* __restrict__ xlane = a.X + c0ld;
+  const typename E::T* __restrict__ xlane = a.X + c0ld;
   const int myh = NH > 1 ? c0ld / a.head_width : 0;
   const int n_piece = a.header[PW_NPIECE];
 
@@ -259,7 +309,7 @@ __global__ __launch_bounds__(kBlock) void agg_hub_pieces_kernel(AggArgs a) {
     const int e0 = rs + k * a.piece_edges;
     const int e1 = min(e0 + a.piece_edges, re);
 
-    RowAcc<W, REDUCE, BRANCH2> acc;
+    RowAcc<E, W, REDUCE, BRANCH2> acc;
     acc.reset();
     for (int ec = e0; ec < e1; ec += kWave) {
       const int me = min(ec + lane, e1 - 1);
@@ -269,13 +319,13 @@ __global__ __launch_bounds__(kBlock) void agg_hub_pieces_kernel(AggArgs a) {
       for (int h = 0; h < NH; ++h) wv[h] = WEIGHTED ? a.val[(int64_t)me * NH + h] : 1.f;
       const int n = min(kWave, e1 - ec);
       for (int jb = 0; jb < n; jb += U) {
-        float v[U][W];
+        typename E::template Raw<W> v[U];
         int cj[U];
 #pragma unroll
         for (int j = 0; j < U; ++j) {
           cj[j] = bcast_i(cv, jb + j);
           const int c = BRANCH2 ? (cj[j] & 0x7fffffff) : cj[j];
-          load_vec<W>(xlane + (int64_t)c * a.ldx, v[j]);
+          E::template load_raw<W>(xlane + (int64_t)c * a.ldx, v[j]);
         }
 #pragma unroll
         for (int j = 0; j < U; ++j) {
@@ -293,16 +343,16 @@ __global__ __launch_bounds__(kBlock) void agg_hub_pieces_kernel(AggArgs a) {
       }
     }
     if (lane_on) {
-      store_vec<W>(a.part + (int64_t)p * a.d + c0, acc.a);
-      if constexpr (BRANCH2) store_vec<W>(a.part2 + (int64_t)p * a.d + c0, acc.b);
-      if constexpr (REDUCE == MP_MAX) store_ivec<W>(a.part_arg + (int64_t)p * a.d + c0, acc.arg);
+      store_f32<W>(a.part + (int64_t)p * a.d + c0, acc.a);
+      if constexpr (BRANCH2) store_f32<W>(a.part2 + (int64_t)p * a.d + c0, acc.b);
+      if constexpr (REDUCE == MP_MAX) store_i32<W>(a.part_arg + (int64_t)p * a.d + c0, acc.arg);
     }
   }
 }
 
 // Hub path 2/2: combine a hub row's pieces in piece order, run the epilogue, store.
-template <int W, int REDUCE, bool BRANCH2>
-__global__ __launch_bounds__(kBlock) void agg_hub_finalize_kernel(AggArgs a) {
+template <class E, int W, int REDUCE, bool BRANCH2>
+__global__ __launch_bounds__(kBlock) void agg_hub_finalize_kernel(AggArgs<E> a) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int c0 = (blockIdx.y * kWave + lane) * W;
@@ -315,14 +365,14 @@ __global__ __launch_bounds__(kBlock) void agg_hub_finalize_kernel(AggArgs a) {
     const int base = a.hub_base[h];
     const int np = a.hub_np[h];
     const int deg = a.rowptr[row + 1] - a.rowptr[row];
-    RowAcc<W, REDUCE, BRANCH2> acc;
+    RowAcc<E, W, REDUCE, BRANCH2> acc;
     acc.reset();
     for (int p = base; p < base + np; ++p) {
       float v[W];
-      load_vec<W>(a.part + (int64_t)p * a.d + c0ld, v);
+      load_f32<W>(a.part + (int64_t)p * a.d + c0ld, v);
       if constexpr (REDUCE == MP_MAX) {
         int ai[W];
-        load_ivec<W>(a.part_arg + (int64_t)p * a.d + c0ld, ai);
+        load_i32<W>(a.part_arg + (int64_t)p * a.d + c0ld, ai);
 #pragma unroll
         for (int k = 0; k < W; ++k)
           if (v[k] > acc.a[k]) { acc.a[k] = v[k]; acc.arg[k] = ai[k]; }
@@ -332,12 +382,12 @@ __global__ __launch_bounds__(kBlock) void agg_hub_finalize_kernel(AggArgs a) {
       }
       if constexpr (BRANCH2) {
         float v2[W];
-        load_vec<W>(a.part2 + (int64_t)p * a.d + c0ld, v2);
+        load_f32<W>(a.part2 + (int64_t)p * a.d + c0ld, v2);
 #pragma unroll
         for (int k = 0; k < W; ++k) acc.b[k] += v2[k];
       }
     }
-    finish_row<W, REDUCE, BRANCH2>(a, row, deg, acc, c0, c0ld, lane_on);
+    finish_row<E, W, REDUCE, BRANCH2, E::kNtFinalize>(a, row, deg, acc, c0, c0ld, lane_on);
   }
 }
 
@@ -444,48 +494,46 @@ __global__ __launch_bounds__(kBlock) void plan_hub_kernel(const int32_t* __restr
 
 // ---- dispatch -------------------------------------------------------------
 
-template <int W, int REDUCE, bool WEIGHTED, bool BRANCH2, int NH = 1>
-static int launch_agg(const AggArgs& a, int64_t N, const int32_t* counts, hipStream_t st) {
-  constexpr int U = 8;
+template <class E, int W, int REDUCE, bool WEIGHTED, bool BRANCH2, int NH = 1>
+static int launch_agg(const AggArgs<E>& a, const int32_t* counts, hipStream_t st) {
+  constexpr int U = E::template kU<W>;
   const int tiles = (int)ceil_div(a.d, kWave * W);
   dim3 grid((unsigned)ceil_div(a.n_seg, kWavesPerBlock), (unsigned)tiles);
-  hipLaunchKernelGGL((agg_rows_kernel<W, REDUCE, WEIGHTED, BRANCH2, U, NH>), grid, dim3(kBlock), 0, st, a);
+  hipLaunchKernelGGL((agg_rows_kernel<E, W, REDUCE, WEIGHTED, BRANCH2, U, NH>), grid, dim3(kBlock), 0, st, a);
   MP_LAUNCH_CHECK();
   const int n_hub = counts[1], n_piece = counts[2];
   if (n_hub > 0) {
     int pb = (int)ceil_div(n_piece, kWavesPerBlock);
     if (pb > kNumCU * 8) pb = kNumCU * 8;
-    hipLaunchKernelGGL((agg_hub_pieces_kernel<W, REDUCE, WEIGHTED, BRANCH2, U, NH>), dim3(pb, tiles),
+    hipLaunchKernelGGL((agg_hub_pieces_kernel<E, W, REDUCE, WEIGHTED, BRANCH2, U, NH>), dim3(pb, tiles),
                        dim3(kBlock), 0, st, a);
     MP_LAUNCH_CHECK();
     int hb = (int)ceil_div(n_hub, kWavesPerBlock);
     if (hb > kNumCU * 8) hb = kNumCU * 8;
-    hipLaunchKernelGGL((agg_hub_finalize_kernel<W, REDUCE, BRANCH2>), dim3(hb, tiles), dim3(kBlock),
+    hipLaunchKernelGGL((agg_hub_finalize_kernel<E, W, REDUCE, BRANCH2>), dim3(hb, tiles), dim3(kBlock),
                        0, st, a);
     MP_LAUNCH_CHECK();
   }
-  (void)N;
   return MP_OK;
 }
 
-template <int W, bool BRANCH2>
-static int dispatch_reduce(const AggArgs& a, int64_t N, const int32_t* counts, int reduce,
-                           hipStream_t st) {
+template <class E, int W>
+static int dispatch_reduce(const AggArgs<E>& a, const int32_t* counts, int reduce, hipStream_t st) {
   const bool weighted = a.val != nullptr;
-  if constexpr (BRANCH2) {
-    return weighted ? launch_agg<W, MP_SUM, true, true>(a, N, counts, st)
-                    : launch_agg<W, MP_SUM, false, true>(a, N, counts, st);
+  if (a.Q != nullptr) {
+    return weighted ? launch_agg<E, W, MP_SUM, true, true>(a, counts, st)
+                    : launch_agg<E, W, MP_SUM, false, true>(a, counts, st);
   }
   switch (reduce) {
     case MP_SUM:
-      return weighted ? launch_agg<W, MP_SUM, true, false>(a, N, counts, st)
-                      : launch_agg<W, MP_SUM, false, false>(a, N, counts, st);
+      return weighted ? launch_agg<E, W, MP_SUM, true, false>(a, counts, st)
+                      : launch_agg<E, W, MP_SUM, false, false>(a, counts, st);
     case MP_MEAN:
-      return weighted ? launch_agg<W, MP_MEAN, true, false>(a, N, counts, st)
-                      : launch_agg<W, MP_MEAN, false, false>(a, N, counts, st);
+      return weighted ? launch_agg<E, W, MP_MEAN, true, false>(a, counts, st)
+                      : launch_agg<E, W, MP_MEAN, false, false>(a, counts, st);
     case MP_MAX:
-      return weighted ? launch_agg<W, MP_MAX, true, false>(a, N, counts, st)
-                      : launch_agg<W, MP_MAX, false, false>(a, N, counts, st);
+      return weighted ? launch_agg<E, W, MP_MAX, true, false>(a, counts, st)
+                      : launch_agg<E, W, MP_MAX, false, false>(a, counts, st);
   }
   return MP_ERR_INVALID_ARG;
 }
@@ -493,29 +541,31 @@ static int dispatch_reduce(const AggArgs& a, int64_t N, const int32_t* counts, i
 static bool aligned(const void* p, size_t a) { return p == nullptr || ((uintptr_t)p % a) == 0; }
 
 // widest per-lane vector every operand allows, then no wider than the row needs
-static int pick_width(const AggArgs& a) {
+template <class E>
+static int pick_width(const AggArgs<E>& a) {
   auto ok = [&](int w) {
-    const size_t bytes = 4u * w;
+    const size_t eb = sizeof(typename E::T) * w;   // X, S, Y, Q: one access of w elements per lane
+    const size_t fb = 4u * (w < 4 ? w : 4);        // fp32 / int32 operands: vectors of at most 4
     if (a.d % w) return false;
     if (a.head_width > 0 && a.head_width % w) return false;   // a lane's columns stay inside one head
     if (a.ldx % w || a.ldy % w) return false;
     if (a.Q && a.ldq % w) return false;
     if (a.S && a.lds % w) return false;
-    return aligned(a.X, bytes) && aligned(a.Y, bytes) && aligned(a.Q, bytes) &&
-           aligned(a.S, bytes) && aligned(a.bias, bytes) && aligned(a.col_scale, bytes) &&
-           aligned(a.argmax, bytes) &&
-           aligned(a.part, bytes) && aligned(a.part2, bytes) && aligned(a.part_arg, bytes);
+    return aligned(a.X, eb) && aligned(a.Y, eb) && aligned(a.Q, eb) && aligned(a.S, eb) &&
+           aligned(a.bias, fb) && aligned(a.col_scale, fb) && aligned(a.argmax, fb) &&
+           aligned(a.part, fb) && aligned(a.part2, fb) && aligned(a.part_arg, fb);
   };
-  int w = 4;
+  int w = E::kMaxW;
   while (w > 1 && !ok(w)) w >>= 1;
-  while (w > 1 && kWave * (w / 2) >= a.d) w >>= 1;  // d=128 -> 2, d=64 -> 1: keep all lanes busy
+  while (w > 1 && kWave * (w / 2) >= a.d) w >>= 1;  // d = 256 -> 4, d = 128 -> 2, d = 64 -> 1: keep all lanes busy
   return w;
 }
 
+template <class E>
 static int agg_common(const int32_t* rowptr, const int32_t* col, const float* val, int64_t N,
-                      const int32_t* plan, const int32_t* counts, const float* X, int64_t ldx,
-                      float* Y, int64_t ldy, float* Q, int64_t ldq, int32_t d, int reduce,
-                      const float* S, int64_t lds, float self_scale, const float* bias, int act,
+                      const int32_t* plan, const int32_t* counts, const typename E::T* X, int64_t ldx,
+                      typename E::T* Y, int64_t ldy, typename E::T* Q, int64_t ldq, int32_t d, int reduce,
+                      const typename E::T* S, int64_t lds, float self_scale, const float* bias, int act,
                       int32_t* argmax, void* ws, size_t ws_bytes, hipStream_t st,
                       const float* col_scale = nullptr, int l2norm = 0, float l2_eps = 1e-12f, int heads = 1) {
   if (!rowptr || !plan || !counts || !X || !Y) return MP_ERR_INVALID_ARG;
@@ -534,7 +584,7 @@ static int agg_common(const int32_t* rowptr, const int32_t* col, const float* va
   mp_spmm_ws_bytes(counts, d, reduce, Q != nullptr, &need);
   if (need > 0 && (!ws || ws_bytes < need)) return MP_ERR_WORKSPACE;
 
-  AggArgs a;
+  AggArgs<E> a;
   a.rowptr = rowptr; a.col = col; a.val = val;
   a.header = plan;
   a.seg_row = plan + PW_HEADER_WORDS;
@@ -565,33 +615,35 @@ static int agg_common(const int32_t* rowptr, const int32_t* col, const float* va
 
   const int w = pick_width(a);
   if (l2norm && d > kWave * w) return MP_ERR_UNSUPPORTED;   // the row must sit in one wave
-  if (heads > 1) {
-    if (!val || Q || reduce != MP_SUM || d % heads) return MP_ERR_INVALID_ARG;
+  if constexpr (E::kExtras) {
+    if (heads > 1) {
+      if (!val || Q || reduce != MP_SUM || d % heads) return MP_ERR_INVALID_ARG;
 #define MP_HEADS(WV)                                                                           \
-    switch (heads) {                                                                           \
-      case 2: return launch_agg<WV, MP_SUM, true, false, 2>(a, N, counts, st);                \
-      case 4: return launch_agg<WV, MP_SUM, true, false, 4>(a, N, counts, st);                \
-      case 8: return launch_agg<WV, MP_SUM, true, false, 8>(a, N, counts, st);                \
-      default: return MP_ERR_UNSUPPORTED;                                                      \
-    }
-    if (w == 4) { MP_HEADS(4) } else if (w == 2) { MP_HEADS(2) } else { MP_HEADS(1) }
+      switch (heads) {                                                                         \
+        case 2: return launch_agg<E, WV, MP_SUM, true, false, 2>(a, counts, st);              \
+        case 4: return launch_agg<E, WV, MP_SUM, true, false, 4>(a, counts, st);              \
+        case 8: return launch_agg<E, WV, MP_SUM, true, false, 8>(a, counts, st);              \
+        default: return MP_ERR_UNSUPPORTED;                                                    \
+      }
+      if (w == 4) { MP_HEADS(4) } else if (w == 2) { MP_HEADS(2) } else { MP_HEADS(1) }
 #undef MP_HEADS
+    }
   }
-  const bool two = Q != nullptr;
+  if constexpr (E::kMaxW == 8) {
+    if (w == 8) return dispatch_reduce<E, 8>(a, counts, reduce, st);
+  }
   switch (w) {
-    case 4: return two ? dispatch_reduce<4, true>(a, N, counts, reduce, st)
-                       : dispatch_reduce<4, false>(a, N, counts, reduce, st);
-    case 2: return two ? dispatch_reduce<2, true>(a, N, counts, reduce, st)
-                       : dispatch_reduce<2, false>(a, N, counts, reduce, st);
-    default: return two ? dispatch_reduce<1, true>(a, N, counts, reduce, st)
-                        : dispatch_reduce<1, false>(a, N, counts, reduce, st);
+    case 4: return dispatch_reduce<E, 4>(a, counts, reduce, st);
+    case 2: return dispatch_reduce<E, 2>(a, counts, reduce, st);
+    default: return dispatch_reduce<E, 1>(a, counts, reduce, st);
   }
 }
 
+template <class E>
 __global__ __launch_bounds__(kBlock) void max_bwd_kernel(const int32_t* __restrict__ col,
                                                          const float* __restrict__ val,
                                                          const int32_t* __restrict__ argmax,
-                                                         const float* __restrict__ dY, int64_t ldy,
+                                                         const typename E::T* __restrict__ dY, int64_t ldy,
                                                          int64_t N, int32_t d, float* dX, int64_t ldx) {
   const int64_t total = N * d;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
@@ -599,7 +651,7 @@ __global__ __launch_bounds__(kBlock) void max_bwd_kernel(const int32_t* __restri
     const int64_t r = i / d;
     const int c = (int)(i - r * d);
     const int e = argmax[i];
-    if (e >= 0) atomicAdd(&dX[(int64_t)col[e] * ldx + c], (val ? val[e] : 1.f) * dY[r * ldy + c]);
+    if (e >= 0) atomicAdd(&dX[(int64_t)col[e] * ldx + c], (val ? val[e] : 1.f) * E::to_f32(dY[r * ldy + c]));
   }
 }
 
@@ -670,8 +722,8 @@ int mp_spmm_csr_f32(const int32_t* rowptr, const int32_t* col, const float* val,
                     float* Y, int64_t ldy, int32_t d, int reduce, const float* S, int64_t lds,
                     float self_scale, const float* bias, int act, int32_t* argmax, void* ws,
                     size_t ws_bytes, mp_stream_t stream) {
-  return agg_common(rowptr, col, val, N, plan, counts_host, X, ldx, Y, ldy, nullptr, 0, d, reduce, S,
-                    lds, self_scale, bias, act, argmax, ws, ws_bytes, as_stream(stream));
+  return agg_common<F32>(rowptr, col, val, N, plan, counts_host, X, ldx, Y, ldy, nullptr, 0, d, reduce, S,
+                         lds, self_scale, bias, act, argmax, ws, ws_bytes, as_stream(stream));
 }
 
 int mp_spmm_csr_epilogue_f32(const int32_t* rowptr, const int32_t* col, const float* val, int64_t N,
@@ -679,9 +731,9 @@ int mp_spmm_csr_epilogue_f32(const int32_t* rowptr, const int32_t* col, const fl
                              float* Y, int64_t ldy, int32_t d, int reduce, const float* S, int64_t lds,
                              float self_scale, const float* col_scale, const float* col_shift, int act,
                              int l2_normalize, float l2_eps, void* ws, size_t ws_bytes, mp_stream_t stream) {
-  return agg_common(rowptr, col, val, N, plan, counts_host, X, ldx, Y, ldy, nullptr, 0, d, reduce, S, lds,
-                    self_scale, col_shift, act, nullptr, ws, ws_bytes, as_stream(stream), col_scale,
-                    l2_normalize ? 1 : 0, l2_eps);
+  return agg_common<F32>(rowptr, col, val, N, plan, counts_host, X, ldx, Y, ldy, nullptr, 0, d, reduce, S, lds,
+                         self_scale, col_shift, act, nullptr, ws, ws_bytes, as_stream(stream), col_scale,
+                         l2_normalize ? 1 : 0, l2_eps);
 }
 
 int mp_idgnn_agg_f32(const int32_t* rowptr, const int32_t* col_marked, const float* val, int64_t N,
@@ -689,24 +741,55 @@ int mp_idgnn_agg_f32(const int32_t* rowptr, const int32_t* col_marked, const flo
                      float* P, int64_t ldp, float* Q, int64_t ldq, int32_t d, void* ws,
                      size_t ws_bytes, mp_stream_t stream) {
   if (!Q) return MP_ERR_INVALID_ARG;
-  return agg_common(rowptr, col_marked, val, N, plan, counts_host, X, ldx, P, ldp, Q, ldq, d, MP_SUM,
-                    nullptr, 0, 0.f, nullptr, MP_ACT_NONE, nullptr, ws, ws_bytes, as_stream(stream));
+  return agg_common<F32>(rowptr, col_marked, val, N, plan, counts_host, X, ldx, P, ldp, Q, ldq, d, MP_SUM,
+                         nullptr, 0, 0.f, nullptr, MP_ACT_NONE, nullptr, ws, ws_bytes, as_stream(stream));
 }
 
 int mp_spmm_csr_heads_f32(const int32_t* rowptr, const int32_t* col, const float* a, int64_t N, const int32_t* plan,
                           const int32_t* counts_host, int32_t heads, const float* V, int64_t ldv, float* Y, int64_t ldy,
                           int32_t d, void* ws, size_t ws_bytes, mp_stream_t stream) {
   if (heads < 1 || !a) return MP_ERR_INVALID_ARG;
-  return agg_common(rowptr, col, a, N, plan, counts_host, V, ldv, Y, ldy, nullptr, 0, d, MP_SUM, nullptr, 0, 0.f,
-                    nullptr, MP_ACT_NONE, nullptr, ws, ws_bytes, as_stream(stream), nullptr, 0, 1e-12f, heads);
+  return agg_common<F32>(rowptr, col, a, N, plan, counts_host, V, ldv, Y, ldy, nullptr, 0, d, MP_SUM, nullptr, 0, 0.f,
+                         nullptr, MP_ACT_NONE, nullptr, ws, ws_bytes, as_stream(stream), nullptr, 0, 1e-12f, heads);
 }
 
 int mp_spmm_max_bwd_f32(const int32_t* col, const float* val, const int32_t* argmax, const float* dY,
                         int64_t ldy, int64_t N, int32_t d, float* dX, int64_t ldx, mp_stream_t stream) {
   if (!col || !argmax || !dY || !dX || N < 0 || d <= 0) return MP_ERR_INVALID_ARG;
   if (N == 0) return MP_OK;
-  hipLaunchKernelGGL(max_bwd_kernel, dim3(flat_grid(N * d)), dim3(kBlock), 0, as_stream(stream), col,
+  hipLaunchKernelGGL(max_bwd_kernel<F32>, dim3(flat_grid(N * d)), dim3(kBlock), 0, as_stream(stream), col,
                      val, argmax, dY, ldy, N, d, dX, ldx);
+  MP_LAUNCH_CHECK();
+  return MP_OK;
+}
+
+int mp_spmm_csr_bf16(const int32_t* rowptr, const int32_t* col, const float* val, int64_t N,
+                     const int32_t* plan, const int32_t* counts_host, const void* X, int64_t ldx,
+                     void* Y, int64_t ldy, int32_t d, int reduce, const void* S, int64_t lds,
+                     float self_scale, const float* bias, int act, int32_t* argmax, void* ws,
+                     size_t ws_bytes, mp_stream_t stream) {
+  return agg_common<Bf16>(rowptr, col, val, N, plan, counts_host, (const uint16_t*)X, ldx, (uint16_t*)Y, ldy,
+                          nullptr, 0, d, reduce, (const uint16_t*)S, lds, self_scale, bias, act, argmax, ws, ws_bytes,
+                          as_stream(stream));
+}
+
+int mp_idgnn_agg_bf16(const int32_t* rowptr, const int32_t* col_marked, const float* val, int64_t N,
+                      const int32_t* plan, const int32_t* counts_host, const void* X, int64_t ldx,
+                      void* P, int64_t ldp, void* Q, int64_t ldq, int32_t d, void* ws,
+                      size_t ws_bytes, mp_stream_t stream) {
+  if (!Q) return MP_ERR_INVALID_ARG;
+  return agg_common<Bf16>(rowptr, col_marked, val, N, plan, counts_host, (const uint16_t*)X, ldx, (uint16_t*)P, ldp,
+                          (uint16_t*)Q, ldq, d, MP_SUM, nullptr, 0, 0.f, nullptr, MP_ACT_NONE, nullptr, ws, ws_bytes,
+                          as_stream(stream));
+}
+
+int mp_spmm_max_bwd_bf16(const int32_t* col, const float* val, const int32_t* argmax, const void* dY,
+                         int64_t ldy, int64_t N, int32_t d, float* dX, int64_t ldx, mp_stream_t stream) {
+  if (!col || !argmax || !dY || !dX || N < 0 || d <= 0) return MP_ERR_INVALID_ARG;
+  if (N >= INT32_MAX) return MP_ERR_UNSUPPORTED;
+  if (N == 0) return MP_OK;
+  hipLaunchKernelGGL(max_bwd_kernel<Bf16>, dim3(flat_grid(N * d)), dim3(kBlock), 0, as_stream(stream), col,
+                     val, argmax, (const uint16_t*)dY, ldy, N, d, dX, ldx);
   MP_LAUNCH_CHECK();
   return MP_OK;
 }

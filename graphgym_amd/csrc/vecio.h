@@ -99,6 +99,104 @@ template <> __device__ __forceinline__ void load_ivec<2>(const int32_t* p, int (
 }
 template <> __device__ __forceinline__ void load_ivec<1>(const int32_t* p, int (&v)[1]) { v[0] = *p; }
 
+// fp32 / int32 operands of up to 8 per lane, as the vectors above (at most 4 wide); W <= 4: exactly load_vec / store_vec
+template <int W> __device__ __forceinline__ void load_f32(const float* p, float (&v)[W]) {
+  if constexpr (W == 8) {
+    float lo[4], hi[4];
+    load_vec<4>(p, lo); load_vec<4>(p + 4, hi);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { v[k] = lo[k]; v[k + 4] = hi[k]; }
+  } else {
+    load_vec<W>(p, v);
+  }
+}
+template <int W> __device__ __forceinline__ void store_f32(float* p, const float (&v)[W]) {
+  if constexpr (W == 8) {
+    const float lo[4] = {v[0], v[1], v[2], v[3]}, hi[4] = {v[4], v[5], v[6], v[7]};
+    store_vec<4>(p, lo); store_vec<4>(p + 4, hi);
+  } else {
+    store_vec<W>(p, v);
+  }
+}
+template <int W> __device__ __forceinline__ void load_i32(const int32_t* p, int (&v)[W]) {
+  if constexpr (W == 8) {
+    int lo[4], hi[4];
+    load_ivec<4>(p, lo); load_ivec<4>(p + 4, hi);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { v[k] = lo[k]; v[k + 4] = hi[k]; }
+  } else {
+    load_ivec<W>(p, v);
+  }
+}
+template <int W> __device__ __forceinline__ void store_i32(int32_t* p, const int (&v)[W]) {
+  if constexpr (W == 8) {
+    const int lo[4] = {v[0], v[1], v[2], v[3]}, hi[4] = {v[4], v[5], v[6], v[7]};
+    store_ivec<4>(p, lo); store_ivec<4>(p + 4, hi);
+  } else {
+    store_ivec<W>(p, v);
+  }
+}
+
+// ---- W bf16 per lane (2W bytes, W <= 8), widened to fp32 exactly (a 16-bit shift) --------------
+
+template <int W> constexpr int bf16_words() { return W == 1 ? 1 : W / 2; }
+
+// W bf16 as packed 32-bit words (element 2i in the low half of word i); W = 1: the low half
+template <int W> __device__ __forceinline__ void load_bf16_raw(const uint16_t* p, uint32_t (&r)[bf16_words<W>()]) {
+  if constexpr (W == 8) {
+    const i32x4 t = *reinterpret_cast<const i32x4*>(p);
+    r[0] = t[0]; r[1] = t[1]; r[2] = t[2]; r[3] = t[3];
+  } else if constexpr (W == 4) {
+    const i32x2 t = *reinterpret_cast<const i32x2*>(p);
+    r[0] = t[0]; r[1] = t[1];
+  } else if constexpr (W == 2) {
+    r[0] = *reinterpret_cast<const uint32_t*>(p);
+  } else {
+    r[0] = *p;
+  }
+}
+
+template <int W> __device__ __forceinline__ void widen_bf16(const uint32_t (&r)[bf16_words<W>()], float (&v)[W]) {
+#pragma unroll
+  for (int k = 0; k < W; ++k)
+    v[k] = __builtin_bit_cast(float, (k & 1) ? (r[k >> 1] & 0xffff0000u) : (r[k >> 1] << 16));
+}
+
+template <int W> __device__ __forceinline__ void load_bf16(const uint16_t* p, float (&v)[W]) {
+  uint32_t r[bf16_words<W>()];
+  load_bf16_raw<W>(p, r);
+  widen_bf16<W>(r, v);
+}
+
+typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+
+// round to nearest even, two values per v_cvt_pk_bf16_f32
+template <int W, bool NT> __device__ __forceinline__ void store_bf16(uint16_t* p, const float (&v)[W]) {
+  if constexpr (W == 1) {
+    const uint16_t h = __builtin_bit_cast(uint16_t, (__bf16)v[0]);
+    if constexpr (NT) __builtin_nontemporal_store(h, p); else *p = h;
+  } else {
+    uint32_t w[W / 2];
+#pragma unroll
+    for (int i = 0; i < W / 2; ++i) {
+      const f32x2 f = {v[2 * i], v[2 * i + 1]};
+      w[i] = __builtin_bit_cast(uint32_t, __builtin_convertvector(f, bf16x2_t));
+    }
+    if constexpr (W == 8) {
+      const i32x4 t = {(int)w[0], (int)w[1], (int)w[2], (int)w[3]};
+      if constexpr (NT) __builtin_nontemporal_store(t, reinterpret_cast<i32x4*>(p));
+      else *reinterpret_cast<i32x4*>(p) = t;
+    } else if constexpr (W == 4) {
+      const i32x2 t = {(int)w[0], (int)w[1]};
+      if constexpr (NT) __builtin_nontemporal_store(t, reinterpret_cast<i32x2*>(p));
+      else *reinterpret_cast<i32x2*>(p) = t;
+    } else {
+      if constexpr (NT) __builtin_nontemporal_store(w[0], reinterpret_cast<uint32_t*>(p));
+      else *reinterpret_cast<uint32_t*>(p) = w[0];
+    }
+  }
+}
+
 __device__ __forceinline__ int bcast_i(int v, int lane) {
   return __builtin_amdgcn_readlane(v, __builtin_amdgcn_readfirstlane(lane));
 }

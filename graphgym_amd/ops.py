@@ -31,29 +31,13 @@ def _agg_in(t, name):
     return t if t.stride(-1) == 1 and t.dim() == 2 else t.contiguous()
 
 
-def _raw_spmm_bf16(g, x, reduce, S=None, self_scale=0.0, bias=None, relu=False, want_argmax=False, col_override=None,
-                   out=None):
-    """one launch of mp_spmm_csr_bf16: bf16 x, S and y, fp32 accumulation, bias passed as fp32; every output is that of
-    mp_spmm_csr_f32 on x.float() with the same plan, rounded once to bf16.  The tile kernels have no bf16 form."""
-    L = lib()
-    N, d = g.num_nodes, x.size(1)
-    y = out if out is not None else placement.empty_or_torch((N, d), x.device, reads=(x,), dtype=torch.bfloat16)
-    if S is not None and S.dtype != torch.bfloat16:
-        S = S.to(torch.bfloat16)
-    b = None if bias is None else bias.detach().to(torch.float32).contiguous()
-    argmax = torch.empty((N, d), dtype=torch.int32, device=x.device) if want_argmax else None
+def _plan_ws(g, device, d, reduce, two_branch):
+    """the plan of g and the workspace a plan-based aggregation of width d needs: (plan, counts, ws, ws_bytes)"""
     plan, counts = g.plan()
-    with torch.cuda.device(x.device):
-        nb = C.c_size_t(0)
-        check(L.mp_spmm_ws_bytes(counts, d, reduce, 0, C.byref(nb)))
-        ws = torch.empty(nb.value, dtype=torch.uint8, device=x.device) if nb.value else None
-        col = g.col if col_override is None else col_override
-        check(L.mp_spmm_csr_bf16(ptr(g.rowptr), ptr(col), ptr(g.val), N, ptr(plan), counts,
-                                 ptr(x), x.stride(0), ptr(y), y.stride(0), d, reduce,
-                                 ptr(S), S.stride(0) if S is not None else 0, float(self_scale),
-                                 ptr(b), _lib.ACT_RELU if relu else _lib.ACT_NONE, ptr(argmax),
-                                 ptr(ws), nb.value, _stream()), "mp_spmm_csr_bf16")
-    return y, argmax
+    nb = C.c_size_t(0)
+    check(lib().mp_spmm_ws_bytes(counts, d, reduce, 1 if two_branch else 0, C.byref(nb)))
+    ws = torch.empty(nb.value, dtype=torch.uint8, device=device) if nb.value else None
+    return plan, counts, ws, nb.value
 
 
 def _raw_spmm(g, x, reduce, S=None, self_scale=0.0, bias=None, relu=False, want_argmax=False,
@@ -62,14 +46,13 @@ def _raw_spmm(g, x, reduce, S=None, self_scale=0.0, bias=None, relu=False, want_
     a large operator, of mp_agg_rows_tiles_f32 (the same aggregation on the producer/consumer tile structure: 2-5 %
     faster; MP_AGG_TILES=0 keeps the plan-based kernel; for an X of >= AGG_HOT_MIN_BYTES its hot-column form,
     mp_agg_rows_tiles_hot_f32: _hot_col) —; x [n_src, d] -> y [N, d] (written into `out` when given).  A bf16 x goes
-    to mp_spmm_csr_bf16 (_raw_spmm_bf16)."""
-    if x.dtype == torch.bfloat16:
-        return _raw_spmm_bf16(g, x, reduce, S=S, self_scale=self_scale, bias=bias, relu=relu, want_argmax=want_argmax,
-                              col_override=col_override, out=out)
+    to mp_spmm_csr_bf16: bf16 x, S and y, fp32 accumulation, bias passed as fp32; every output is that of
+    mp_spmm_csr_f32 on x.float() with the same plan, rounded once to bf16.  The tile kernels have no bf16 form."""
     L = lib()
     N, d = g.num_nodes, x.size(1)
-    y = out if out is not None else placement.empty_or_torch((N, d), x.device, reads=(x,))
-    if (reduce in (_lib.SUM, _lib.MEAN, _lib.MAX) and d in AGG_TILES_WIDTHS and N >= AGG_TILES_MIN_ROWS and bias is None
+    y = out if out is not None else placement.empty_or_torch((N, d), x.device, reads=(x,), dtype=x.dtype)
+    if (x.dtype == torch.float32 and reduce in (_lib.SUM, _lib.MEAN, _lib.MAX) and d in AGG_TILES_WIDTHS
+            and N >= AGG_TILES_MIN_ROWS and bias is None
             and not relu and not want_argmax and col_override is None and not (reduce != _lib.SUM and S is not None)
             and os.environ.get("MP_AGG_TILES", "1") != "0"
             and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0 and y.stride(0) % 4 == 0 and y.data_ptr() % 16 == 0
@@ -89,18 +72,23 @@ def _raw_spmm(g, x, reduce, S=None, self_scale=0.0, bias=None, relu=False, want_
                                               ptr(S), S.stride(0) if S is not None else 0, float(self_scale),
                                               ptr(y), y.stride(0), _stream()), "mp_agg_rows_tiles_f32")
         return y, None
+    if x.dtype == torch.bfloat16:
+        name = "mp_spmm_csr_bf16"
+        if S is not None:
+            S = S.to(torch.bfloat16)
+        if bias is not None:
+            bias = bias.detach().to(torch.float32).contiguous()
+    else:
+        name = "mp_spmm_csr_f32"
     argmax = torch.empty((N, d), dtype=torch.int32, device=x.device) if want_argmax else None
-    plan, counts = g.plan()
+    plan, counts, ws, ws_bytes = _plan_ws(g, x.device, d, reduce, False)
     with torch.cuda.device(x.device):
-        nb = C.c_size_t(0)
-        check(L.mp_spmm_ws_bytes(counts, d, reduce, 0, C.byref(nb)))
-        ws = torch.empty(nb.value, dtype=torch.uint8, device=x.device) if nb.value else None
         col = g.col if col_override is None else col_override
-        check(L.mp_spmm_csr_f32(ptr(g.rowptr), ptr(col), ptr(g.val), N, ptr(plan), counts,
-                                ptr(x), x.stride(0), ptr(y), y.stride(0), d, reduce,
-                                ptr(S), S.stride(0) if S is not None else 0, float(self_scale),
-                                ptr(bias), _lib.ACT_RELU if relu else _lib.ACT_NONE, ptr(argmax),
-                                ptr(ws), nb.value, _stream()), "mp_spmm_csr_f32")
+        check(getattr(L, name)(ptr(g.rowptr), ptr(col), ptr(g.val), N, ptr(plan), counts,
+                               ptr(x), x.stride(0), ptr(y), y.stride(0), d, reduce,
+                               ptr(S), S.stride(0) if S is not None else 0, float(self_scale),
+                               ptr(bias), _lib.ACT_RELU if relu else _lib.ACT_NONE, ptr(argmax),
+                               ptr(ws), ws_bytes, _stream()), name)
     return y, argmax
 
 
@@ -116,26 +104,23 @@ def spmm_fused_eval(g, x, reduce="sum", self_scale=0.0, col_scale=None, col_shif
     L = lib()
     N, d = g.num_nodes, x.size(1)
     y = torch.empty((N, d), dtype=torch.float32, device=x.device)
-    plan, counts = g.plan()
     red = _lib.REDUCE[reduce]
+    plan, counts, ws, ws_bytes = _plan_ws(g, x.device, d, red, False)
     S = x if self_scale != 0.0 else None
     with torch.cuda.device(x.device):
-        nb = C.c_size_t(0)
-        check(L.mp_spmm_ws_bytes(counts, d, red, 0, C.byref(nb)))
-        ws = torch.empty(nb.value, dtype=torch.uint8, device=x.device) if nb.value else None
         cs = None if col_scale is None else col_scale.detach().contiguous()
         ct = None if col_shift is None else col_shift.detach().contiguous()
         st = L.mp_spmm_csr_epilogue_f32(ptr(g.rowptr), ptr(g.col), ptr(g.val), N, ptr(plan), counts, ptr(x),
                                         x.stride(0), ptr(y), y.stride(0), d, red, ptr(S),
                                         S.stride(0) if S is not None else 0, float(self_scale), ptr(cs), ptr(ct),
                                         _lib.ACT_RELU if relu else _lib.ACT_NONE, 1 if l2norm else 0,
-                                        float(l2_eps), ptr(ws), nb.value, _stream())
+                                        float(l2_eps), ptr(ws), ws_bytes, _stream())
         if st == 2 and l2norm:   # row wider than one wave: normalise in a second pass
             check(L.mp_spmm_csr_epilogue_f32(ptr(g.rowptr), ptr(g.col), ptr(g.val), N, ptr(plan), counts, ptr(x),
                                              x.stride(0), ptr(y), y.stride(0), d, red, ptr(S),
                                              S.stride(0) if S is not None else 0, float(self_scale), ptr(cs),
                                              ptr(ct), _lib.ACT_RELU if relu else _lib.ACT_NONE, 0, float(l2_eps),
-                                             ptr(ws), nb.value, _stream()), "mp_spmm_csr_epilogue_f32")
+                                             ptr(ws), ws_bytes, _stream()), "mp_spmm_csr_epilogue_f32")
             return torch.nn.functional.normalize(y, p=2, dim=-1, eps=l2_eps)
         check(st, "mp_spmm_csr_epilogue_f32")
     return y
@@ -579,13 +564,10 @@ def _raw_spmm_heads(g, a, V, heads):
         N, d = g.num_nodes, V.size(1)
         a = a.contiguous()
         y = placement.empty_or_torch((N, d), V.device, reads=(V,))
-        plan, counts = g.plan()
+        plan, counts, ws, ws_bytes = _plan_ws(g, V.device, d, _lib.SUM, False)
         with torch.cuda.device(V.device):
-            nb = C.c_size_t(0)
-            check(L.mp_spmm_ws_bytes(counts, d, _lib.SUM, 0, C.byref(nb)))
-            ws = torch.empty(nb.value, dtype=torch.uint8, device=V.device) if nb.value else None
             st = L.mp_spmm_csr_heads_f32(ptr(g.rowptr), ptr(g.col), ptr(a), N, ptr(plan), counts, heads, ptr(V),
-                                         V.stride(0), ptr(y), y.stride(0), d, ptr(ws), nb.value, _stream())
+                                         V.stride(0), ptr(y), y.stride(0), d, ptr(ws), ws_bytes, _stream())
         if st == 0:
             return y
         if st != 2:
@@ -835,15 +817,12 @@ def _op_spmm_max_bwd_raw(dy: Tensor, argmax: Tensor, graph: int) -> Tensor:
     dy = dy.contiguous()
     N, d = dy.shape
     dx = torch.zeros((g.num_cols, d), dtype=torch.float32, device=dy.device)
-    if dy.dtype == torch.bfloat16:     # fp32 accumulation of the bf16 gradient, rounded once
-        with torch.cuda.device(dy.device):
-            check(lib().mp_spmm_max_bwd_bf16(ptr(g.col), ptr(g.val), ptr(argmax), ptr(dy), dy.stride(0), N, d, ptr(dx),
-                                             dx.stride(0), _stream()), "mp_spmm_max_bwd_bf16")
-        return dx.to(torch.bfloat16)
+    # a bf16 gradient is accumulated in fp32 and rounded once
+    name = "mp_spmm_max_bwd_bf16" if dy.dtype == torch.bfloat16 else "mp_spmm_max_bwd_f32"
     with torch.cuda.device(dy.device):
-        check(lib().mp_spmm_max_bwd_f32(ptr(g.col), ptr(g.val), ptr(argmax), ptr(dy), dy.stride(0), N, d, ptr(dx),
-                                        dx.stride(0), _stream()), "mp_spmm_max_bwd_f32")
-    return dx
+        check(getattr(lib(), name)(ptr(g.col), ptr(g.val), ptr(argmax), ptr(dy), dy.stride(0), N, d, ptr(dx),
+                                   dx.stride(0), _stream()), name)
+    return dx.to(dy.dtype)
 
 
 @_op_spmm_max_bwd_raw.register_fake
@@ -857,22 +836,10 @@ def _op_idgnn_agg_raw(x: Tensor, graph: int, id_index: Tensor) -> Tuple[Tensor, 
     x = _agg_in(x, "x")
     L = lib()
     N, d = g.num_nodes, x.size(1)
-    if x.dtype == torch.bfloat16:     # mp_idgnn_agg_bf16 (plan-based, fp32 accumulation); the tile kernels have no bf16 form
-        P = placement.empty_or_torch((N, d), x.device, reads=(x,), dtype=torch.bfloat16)
-        Q = placement.empty_or_torch((N, d), x.device, reads=(x,), dtype=torch.bfloat16)
-        col_marked = g.mark_ids(id_index)
-        plan, counts = g.plan()
-        with torch.cuda.device(x.device):
-            nb = C.c_size_t(0)
-            check(L.mp_spmm_ws_bytes(counts, d, _lib.SUM, 1, C.byref(nb)))
-            ws = torch.empty(nb.value, dtype=torch.uint8, device=x.device) if nb.value else None
-            check(L.mp_idgnn_agg_bf16(ptr(g.rowptr), ptr(col_marked), ptr(g.val), N, ptr(plan), counts,
-                                      ptr(x), x.stride(0), ptr(P), P.stride(0), ptr(Q), Q.stride(0), d,
-                                      ptr(ws), nb.value, _stream()), "mp_idgnn_agg_bf16")
-        return P, Q
-    P = placement.empty_or_torch((N, d), x.device, reads=(x,))
-    Q = placement.empty_or_torch((N, d), x.device, reads=(x,))
-    if (d in AGG_TILES_WIDTHS and N >= AGG_TILES_MIN_ROWS and os.environ.get("MP_AGG_TILES", "1") != "0"
+    P = placement.empty_or_torch((N, d), x.device, reads=(x,), dtype=x.dtype)
+    Q = placement.empty_or_torch((N, d), x.device, reads=(x,), dtype=x.dtype)
+    if (x.dtype == torch.float32 and d in AGG_TILES_WIDTHS and N >= AGG_TILES_MIN_ROWS
+            and os.environ.get("MP_AGG_TILES", "1") != "0"
             and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0 and g.nnz > 0 and id_index.numel() > 0
             and g.max_row_entries() <= FUSED_MAX_ROW):
         # the tile structure (round 4): P in the pass of mp_agg_rows_tiles_f32, which also writes the zero rows of Q;
@@ -888,15 +855,14 @@ def _op_idgnn_agg_raw(x: Tensor, graph: int, id_index: Tensor) -> Tuple[Tensor, 
                                            Z.stride(0), ptr(P), P.stride(0), ptr(Q), Q.stride(0), _stream()),
                   "mp_idgnn_agg_tiles_f32")
         return P, Q
+    # plan-based: mp_idgnn_agg_f32, or mp_idgnn_agg_bf16 (fp32 accumulation); the tile kernels have no bf16 form
+    name = "mp_idgnn_agg_bf16" if x.dtype == torch.bfloat16 else "mp_idgnn_agg_f32"
     col_marked = g.mark_ids(id_index)
-    plan, counts = g.plan()
+    plan, counts, ws, ws_bytes = _plan_ws(g, x.device, d, _lib.SUM, True)
     with torch.cuda.device(x.device):
-        nb = C.c_size_t(0)
-        check(L.mp_spmm_ws_bytes(counts, d, _lib.SUM, 1, C.byref(nb)))
-        ws = torch.empty(nb.value, dtype=torch.uint8, device=x.device) if nb.value else None
-        check(L.mp_idgnn_agg_f32(ptr(g.rowptr), ptr(col_marked), ptr(g.val), N, ptr(plan), counts,
-                                 ptr(x), x.stride(0), ptr(P), P.stride(0), ptr(Q), Q.stride(0), d,
-                                 ptr(ws), nb.value, _stream()), "mp_idgnn_agg_f32")
+        check(getattr(L, name)(ptr(g.rowptr), ptr(col_marked), ptr(g.val), N, ptr(plan), counts,
+                               ptr(x), x.stride(0), ptr(P), P.stride(0), ptr(Q), Q.stride(0), d,
+                               ptr(ws), ws_bytes, _stream()), name)
     return P, Q
 
 
