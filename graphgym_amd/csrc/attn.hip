@@ -52,14 +52,17 @@ __global__ __launch_bounds__(kBlock) void sddmm_dot_kernel(const int32_t* __rest
 // SGPRs and issues two coalesced row loads per entry — A[row] (an L1/L2 hit while the row repeats)
 // and B[col] — U entries in flight.  The per-head dot product is a wave-segment reduction
 // (lanes of one head are contiguous); scores leave the wave as one coalesced store per 64 entries.
+// MASK (the weight gradient of a weighted max, mp_spmm_heads_max_da_f32): a column's product enters entry e's sum only
+// where e won that column of its row, argmax[row, c] == e — one more coalesced row load (argmax[row], beside A[row]).
 constexpr int kStream = 256;
 
-template <int W, int U>
+template <int W, int U, bool MASK>
 __global__ __launch_bounds__(kBlock) void sddmm_stream_kernel(const int32_t* __restrict__ row_of,
                                                               const int32_t* __restrict__ col, int64_t nnz,
                                                               const float* __restrict__ A, int64_t lda,
                                                               const float* __restrict__ B, int64_t ldb,
-                                                              int32_t d, int32_t heads, float scale, float* s) {
+                                                              int32_t d, int32_t heads, float scale, float* s,
+                                                              const int32_t* __restrict__ argmax, int64_t ldm) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int64_t w0 = ((int64_t)blockIdx.x * kWavesPerBlock + wave) * kStream;
@@ -87,16 +90,22 @@ __global__ __launch_bounds__(kBlock) void sddmm_stream_kernel(const int32_t* __r
         const bool on = c0 < d;
         const int c0ld = on ? c0 : 0;
         float a[U][W], b[U][W];
+        int m[MASK ? U : 1][W];
 #pragma unroll
         for (int j = 0; j < U; ++j) {
           load_vec<W>(A + (int64_t)rj[j] * lda + c0ld, a[j]);
           load_vec<W>(B + (int64_t)cj[j] * ldb + c0ld, b[j]);
+          if constexpr (MASK) load_i32<W>(argmax + (int64_t)rj[j] * ldm + c0ld, m[j]);
         }
 #pragma unroll
         for (int j = 0; j < U; ++j) {
           if (on) {
+            const int e = (int)(ec + jb + j);
 #pragma unroll
-            for (int k = 0; k < W; ++k) acc[j] = fmaf(a[j][k], b[j][k], acc[j]);
+            for (int k = 0; k < W; ++k) {
+              if constexpr (MASK) acc[j] = m[j][k] == e ? fmaf(a[j][k], b[j][k], acc[j]) : acc[j];
+              else acc[j] = fmaf(a[j][k], b[j][k], acc[j]);
+            }
           }
         }
       }
@@ -471,6 +480,36 @@ static int row_grid(int64_t N) {
   return (int)b;
 }
 
+static bool al(const void* p, size_t a) { return ((uintptr_t)p % a) == 0; }
+
+// the entry-balanced launch of both forms: widest vector every operand allows, no wider than the row needs
+template <bool MASK>
+static int sddmm_stream_launch(const int32_t* row_of, const int32_t* col, int64_t nnz, const float* Am, int64_t lda,
+                               const float* Bm, int64_t ldb, int32_t d, int32_t heads, float scale, float* s,
+                               const int32_t* argmax, int64_t ldm, hipStream_t st) {
+  const int dh = d / heads;
+  int w = 4;
+  auto ok = [&](int ww) {
+    return d % ww == 0 && dh % ww == 0 && lda % ww == 0 && ldb % ww == 0 && al(Am, 4u * ww) && al(Bm, 4u * ww) &&
+           (!MASK || (ldm % ww == 0 && al(argmax, 4u * ww)));
+  };
+  while (w > 1 && !ok(w)) w >>= 1;
+  while (w > 1 && kWave * (w / 2) >= d) w >>= 1;
+  if (heads > 1) {
+    const int gs = dh / w;   // lanes per head must be a power of two inside one wave-wide tile
+    if (d > kWave * w || gs < 1 || (gs & (gs - 1)) || kWave % gs) return MP_ERR_UNSUPPORTED;
+  }
+  const int64_t waves = ceil_div(nnz, kStream);
+  dim3 grid((unsigned)ceil_div(waves, kWavesPerBlock));
+  switch (w) {
+    case 4: hipLaunchKernelGGL((sddmm_stream_kernel<4, 4, MASK>), grid, dim3(kBlock), 0, st, row_of, col, nnz, Am, lda, Bm, ldb, d, heads, scale, s, argmax, ldm); break;
+    case 2: hipLaunchKernelGGL((sddmm_stream_kernel<2, 4, MASK>), grid, dim3(kBlock), 0, st, row_of, col, nnz, Am, lda, Bm, ldb, d, heads, scale, s, argmax, ldm); break;
+    default: hipLaunchKernelGGL((sddmm_stream_kernel<1, 4, MASK>), grid, dim3(kBlock), 0, st, row_of, col, nnz, Am, lda, Bm, ldb, d, heads, scale, s, argmax, ldm); break;
+  }
+  MP_LAUNCH_CHECK();
+  return MP_OK;
+}
+
 }  // namespace mp
 
 using namespace mp;
@@ -490,35 +529,26 @@ int mp_sddmm_dot_f32(const int32_t* rowptr, const int32_t* col, int64_t N, int64
   return MP_OK;
 }
 
-static bool al(const void* p, size_t a) { return ((uintptr_t)p % a) == 0; }
-
 int mp_sddmm_dot_stream_f32(const int32_t* row_of, const int32_t* col, int64_t nnz, const float* Am,
                             int64_t lda, const float* Bm, int64_t ldb, int32_t d, int32_t heads, float scale,
                             float* s, mp_stream_t stream) {
   if (nnz < 0 || d <= 0 || heads <= 0 || d % heads) return MP_ERR_INVALID_ARG;
   if (nnz == 0) return MP_OK;
   if (!row_of || !col || !Am || !Bm || !s || lda < d || ldb < d) return MP_ERR_INVALID_ARG;
-  const int dh = d / heads;
-  int w = 4;
-  auto ok = [&](int ww) {
-    return d % ww == 0 && dh % ww == 0 && lda % ww == 0 && ldb % ww == 0 && al(Am, 4u * ww) && al(Bm, 4u * ww);
-  };
-  while (w > 1 && !ok(w)) w >>= 1;
-  while (w > 1 && kWave * (w / 2) >= d) w >>= 1;
-  if (heads > 1) {
-    const int gs = dh / w;   // lanes per head must be a power of two inside one wave-wide tile
-    if (d > kWave * w || gs < 1 || (gs & (gs - 1)) || kWave % gs) return MP_ERR_UNSUPPORTED;
-  }
-  const int64_t waves = ceil_div(nnz, kStream);
-  dim3 grid((unsigned)ceil_div(waves, kWavesPerBlock));
-  hipStream_t st = as_stream(stream);
-  switch (w) {
-    case 4: hipLaunchKernelGGL((sddmm_stream_kernel<4, 4>), grid, dim3(kBlock), 0, st, row_of, col, nnz, Am, lda, Bm, ldb, d, heads, scale, s); break;
-    case 2: hipLaunchKernelGGL((sddmm_stream_kernel<2, 4>), grid, dim3(kBlock), 0, st, row_of, col, nnz, Am, lda, Bm, ldb, d, heads, scale, s); break;
-    default: hipLaunchKernelGGL((sddmm_stream_kernel<1, 4>), grid, dim3(kBlock), 0, st, row_of, col, nnz, Am, lda, Bm, ldb, d, heads, scale, s); break;
-  }
-  MP_LAUNCH_CHECK();
-  return MP_OK;
+  return sddmm_stream_launch<false>(row_of, col, nnz, Am, lda, Bm, ldb, d, heads, scale, s, nullptr, 0,
+                                    as_stream(stream));
+}
+
+int mp_spmm_heads_max_da_f32(const int32_t* row_of, const int32_t* col, int64_t nnz, const int32_t* argmax,
+                             int64_t ldm, const float* dY, int64_t ldy, const float* V, int64_t ldv, int32_t d,
+                             int32_t heads, float* da, mp_stream_t stream) {
+  if (!row_of || !col || !argmax || !dY || !V || !da || nnz < 0 || d <= 0 || heads < 1 || d % heads)
+    return MP_ERR_INVALID_ARG;
+  if (ldm < d || ldy < d || ldv < d) return MP_ERR_INVALID_ARG;
+  if (nnz >= INT32_MAX) return MP_ERR_UNSUPPORTED;
+  if (nnz == 0) return MP_OK;
+  return sddmm_stream_launch<true>(row_of, col, nnz, dY, ldy, V, ldv, d, heads, 1.0f, da, argmax, ldm,
+                                   as_stream(stream));
 }
 
 int mp_sddmm_grad_f32(const int32_t* rowptr, const int32_t* col, int64_t N, int64_t nnz, const float* A,

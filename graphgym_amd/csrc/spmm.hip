@@ -617,16 +617,25 @@ static int agg_common(const int32_t* rowptr, const int32_t* col, const float* va
   if (l2norm && d > kWave * w) return MP_ERR_UNSUPPORTED;   // the row must sit in one wave
   if constexpr (E::kExtras) {
     if (heads > 1) {
-      if (!val || Q || reduce != MP_SUM || d % heads) return MP_ERR_INVALID_ARG;
-#define MP_HEADS(WV)                                                                           \
+      if (!val || Q || d % heads) return MP_ERR_INVALID_ARG;
+      // mean and max take the same body: mean divides by the row's entry count in finish_row, max keeps the first
+      // winning entry per column (argmax, merged across hub pieces in piece order by the finalize kernel)
+#define MP_HEADS_R(WV, R)                                                                      \
       switch (heads) {                                                                         \
-        case 2: return launch_agg<E, WV, MP_SUM, true, false, 2>(a, counts, st);              \
-        case 4: return launch_agg<E, WV, MP_SUM, true, false, 4>(a, counts, st);              \
-        case 8: return launch_agg<E, WV, MP_SUM, true, false, 8>(a, counts, st);              \
+        case 2: return launch_agg<E, WV, R, true, false, 2>(a, counts, st);                   \
+        case 4: return launch_agg<E, WV, R, true, false, 4>(a, counts, st);                   \
+        case 8: return launch_agg<E, WV, R, true, false, 8>(a, counts, st);                   \
         default: return MP_ERR_UNSUPPORTED;                                                    \
+      }
+#define MP_HEADS(WV)                                                                           \
+      switch (reduce) {                                                                        \
+        case MP_SUM: MP_HEADS_R(WV, MP_SUM)                                                    \
+        case MP_MEAN: MP_HEADS_R(WV, MP_MEAN)                                                  \
+        default: MP_HEADS_R(WV, MP_MAX)                                                        \
       }
       if (w == 4) { MP_HEADS(4) } else if (w == 2) { MP_HEADS(2) } else { MP_HEADS(1) }
 #undef MP_HEADS
+#undef MP_HEADS_R
     }
   }
   if constexpr (E::kMaxW == 8) {
@@ -652,6 +661,24 @@ __global__ __launch_bounds__(kBlock) void max_bwd_kernel(const int32_t* __restri
     const int c = (int)(i - r * d);
     const int e = argmax[i];
     if (e >= 0) atomicAdd(&dX[(int64_t)col[e] * ldx + c], (val ? val[e] : 1.f) * E::to_f32(dY[r * ldy + c]));
+  }
+}
+
+// Backward of the multi-head weighted max into V: dV[col[e], c] += a[e * H + c / hw] * dY[r, c] for e = argmax[r, c].
+// One wave per output row (no 64-bit index division), lanes across the columns: argmax and dY are read coalesced, the
+// adds are no-return float atomics (global_atomic_add_f32), one launch for every head.
+__global__ __launch_bounds__(kBlock) void heads_max_bwd_kernel(const int32_t* __restrict__ col,
+                                                               const float* __restrict__ a, int32_t heads, int32_t hw,
+                                                               const int32_t* __restrict__ argmax,
+                                                               const float* __restrict__ dY, int64_t ldy, int64_t N,
+                                                               int32_t d, float* dV, int64_t ldv) {
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  for (int64_t r = (int64_t)blockIdx.x * kWavesPerBlock + wave; r < N; r += (int64_t)gridDim.x * kWavesPerBlock) {
+    for (int c = lane; c < d; c += kWave) {
+      const int e = argmax[r * d + c];
+      if (e >= 0) atomicAdd(&dV[(int64_t)col[e] * ldv + c], a[(int64_t)e * heads + c / hw] * dY[r * ldy + c]);
+    }
   }
 }
 
@@ -751,6 +778,31 @@ int mp_spmm_csr_heads_f32(const int32_t* rowptr, const int32_t* col, const float
   if (heads < 1 || !a) return MP_ERR_INVALID_ARG;
   return agg_common<F32>(rowptr, col, a, N, plan, counts_host, V, ldv, Y, ldy, nullptr, 0, d, MP_SUM, nullptr, 0, 0.f,
                          nullptr, MP_ACT_NONE, nullptr, ws, ws_bytes, as_stream(stream), nullptr, 0, 1e-12f, heads);
+}
+
+int mp_spmm_csr_heads_reduce_f32(const int32_t* rowptr, const int32_t* col, const float* a, int64_t N,
+                                 const int32_t* plan, const int32_t* counts_host, int32_t heads, int reduce,
+                                 const float* V, int64_t ldv, float* Y, int64_t ldy, int32_t d, int32_t* argmax,
+                                 void* ws, size_t ws_bytes, mp_stream_t stream) {
+  if (heads < 1 || !a || !col || d <= 0 || d % heads) return MP_ERR_INVALID_ARG;
+  if (reduce < MP_SUM || reduce > MP_MAX) return MP_ERR_INVALID_ARG;
+  return agg_common<F32>(rowptr, col, a, N, plan, counts_host, V, ldv, Y, ldy, nullptr, 0, d, reduce, nullptr, 0, 0.f,
+                         nullptr, MP_ACT_NONE, reduce == MP_MAX ? argmax : nullptr, ws, ws_bytes, as_stream(stream),
+                         nullptr, 0, 1e-12f, heads);
+}
+
+int mp_spmm_heads_max_bwd_f32(const int32_t* col, const float* a, int32_t heads, const int32_t* argmax, int64_t N,
+                              int32_t d, const float* dY, int64_t ldy, float* dV, int64_t ldv, mp_stream_t stream) {
+  if (!col || !a || !argmax || !dY || !dV || N < 0 || d <= 0 || heads < 1 || d % heads) return MP_ERR_INVALID_ARG;
+  if (ldy < d || ldv < d) return MP_ERR_INVALID_ARG;
+  if (N >= INT32_MAX) return MP_ERR_UNSUPPORTED;
+  if (N == 0) return MP_OK;
+  int64_t blocks = ceil_div(N, kWavesPerBlock);
+  if (blocks > kNumCU * 16) blocks = kNumCU * 16;
+  hipLaunchKernelGGL(heads_max_bwd_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), col, a, heads,
+                     d / heads, argmax, dY, ldy, N, d, dV, ldv);
+  MP_LAUNCH_CHECK();
+  return MP_OK;
 }
 
 int mp_spmm_max_bwd_f32(const int32_t* col, const float* val, const int32_t* argmax, const float* dY,

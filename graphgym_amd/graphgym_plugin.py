@@ -8,12 +8,15 @@ Importing this module is the whole integration:
     'Tfg-idgcn', 'Tfg-idsage', 'Tfg-idgat', 'Tfg-idgin' (config/*_tf/*.yaml:29, dispatched
     by main_zd.py:299-308 in the reference),
   * the built-in keys 'gcnconv', 'sageconv', 'gatconv', 'ginconv', 'generalconv'
-    (graphgym/models/layer.py:224-235).
+    (graphgym/models/layer.py:224-235),
+  * the design-space attention keys 'gaddconv', 'gmulconv' (graphgym/contrib/layer/attconv.py:239-240),
+    installed by install_design() — kept apart from ALL_KEYS, the ID-GNN path's keys that install() returns.
 
 ``register_layer`` raises KeyError on a duplicate (register.py:6-10), and built-ins shadow
 registered keys (layer.py:238), so taking over an existing key is done by assignment into the
 dictionaries — ``install(override=True)``, the default.
 """
+from . import attconv as A
 from . import layers as L
 from . import registry as R
 
@@ -42,13 +45,13 @@ BUILTIN_KEYS = {
     'generalconv': L.GeneralConv,
 }
 ALL_KEYS = {**ID_KEYS, **TF_KEYS, **BUILTIN_KEYS}
+DESIGN_KEYS = {
+    'gaddconv': A.GeneralAddAttConv,
+    'gmulconv': A.GeneralMulAttConv,
+}
 
 
-def install(override=True):
-    """Register every key; returns the list of keys now served by the engine.
-
-    override=False keeps the reference's semantics strictly: keys that already exist are
-    left alone (register_layer would raise KeyError)."""
+def _install_keys(keys, override):
     taken = []
     dicts = [R.layer_dict]
     try:  # the resolved dictionaries GeneralLayer actually indexes (layer.py:24,238)
@@ -59,7 +62,7 @@ def install(override=True):
                 dicts.append(mod.layer_dict)
     except Exception:
         pass
-    for key, cls in ALL_KEYS.items():
+    for key, cls in keys.items():
         for d in dicts:
             if key in d and d[key] is not cls:
                 if override:
@@ -74,7 +77,21 @@ def install(override=True):
     return taken
 
 
+def install(override=True):
+    """Register every key of ALL_KEYS; returns the list of keys now served by the engine.
+
+    override=False keeps the reference's semantics strictly: keys that already exist are
+    left alone (register_layer would raise KeyError)."""
+    return _install_keys(ALL_KEYS, override)
+
+
+def install_design(override=True):
+    """Register the design-space attention keys of DESIGN_KEYS with install()'s semantics; returns the keys taken."""
+    return _install_keys(DESIGN_KEYS, override)
+
+
 installed_keys = install(override=True)
+installed_design_keys = install_design(override=True)
 
 
 # ---- the post-ops of GraphGym's layer wrapper on the engine -------------------------------------------------

@@ -739,8 +739,112 @@ class _SpmmEdgeValues(torch.autograd.Function):
         return da, dV, None, None
 
 
-def spmm_edge_values(g, a, V, heads=1):
-    return _SpmmEdgeValues.apply(a, V, g, int(heads))
+def _raw_spmm_heads_reduce(g, a, V, heads, reduce):
+    """y[i, slice h] = mean / max over the entries e of row i of a[e,h] V[col_e, slice h] -> (y, argmax [N, d] int32 for
+    max, else None).  One launch of the plan kernel for all heads (mp_spmm_csr_heads_reduce_f32); one weight per entry
+    is the weighted plan aggregation itself; other head counts run one launch per head on column slices."""
+    want = reduce == _lib.MAX
+    if heads == 1:
+        return _raw_spmm(g.with_values(a.reshape(-1).contiguous()), V, reduce, want_argmax=want)
+    L = lib()
+    N, d = g.num_nodes, V.size(1)
+    a = a.contiguous()
+    argmax = torch.empty((N, d), dtype=torch.int32, device=V.device) if want else None
+    if heads in (2, 4, 8):
+        y = placement.empty_or_torch((N, d), V.device, reads=(V,))
+        plan, counts, ws, ws_bytes = _plan_ws(g, V.device, d, reduce, False)
+        with torch.cuda.device(V.device):
+            st = L.mp_spmm_csr_heads_reduce_f32(ptr(g.rowptr), ptr(g.col), ptr(a), N, ptr(plan), counts, heads, reduce,
+                                                ptr(V), V.stride(0), ptr(y), y.stride(0), d, ptr(argmax), ptr(ws),
+                                                ws_bytes, _stream())
+        if st == 0:
+            return y, argmax
+        if st != 2:
+            check(st, "mp_spmm_csr_heads_reduce_f32")
+    dh = d // heads
+    y = torch.empty((N, d), dtype=torch.float32, device=V.device)
+    for h in range(heads):
+        cs = slice(h * dh, (h + 1) * dh)
+        _, am = _raw_spmm(g.with_values(a[:, h].contiguous()), V[:, cs], reduce, want_argmax=want, out=y[:, cs])
+        if want:
+            argmax[:, cs] = am
+    return y, argmax
+
+
+def _raw_heads_max_da(g, argmax, dy, V, heads):
+    """da[e, h] = sum over the columns c of head h that entry e won (argmax[row_e, c] == e) of dy[row_e, c] V[col_e, c]
+    (mp_spmm_heads_max_da_f32; head layouts it does not take: per head on column slices)"""
+    L = lib()
+    nnz, d = g.nnz, V.size(1)
+    da = torch.empty((max(nnz, 1), heads), dtype=torch.float32, device=V.device)
+    with torch.cuda.device(V.device):
+        st = L.mp_spmm_heads_max_da_f32(ptr(g.row_ids()), ptr(g.col), nnz, ptr(argmax), argmax.stride(0), ptr(dy),
+                                        dy.stride(0), ptr(V), V.stride(0), d, heads, ptr(da), _stream())
+        if st != 2:
+            check(st, "mp_spmm_heads_max_da_f32")
+            return da[:nnz]
+        dh = d // heads
+        one = torch.empty(max(nnz, 1), dtype=torch.float32, device=V.device)
+        for h in range(heads):
+            cs = slice(h * dh, (h + 1) * dh)
+            check(L.mp_spmm_heads_max_da_f32(ptr(g.row_ids()), ptr(g.col), nnz, ptr(argmax[:, cs]), argmax.stride(0),
+                                             ptr(dy[:, cs]), dy.stride(0), ptr(V[:, cs]), V.stride(0), dh, 1, ptr(one),
+                                             _stream()), "mp_spmm_heads_max_da_f32")
+            da[:, h] = one
+    return da[:nnz]
+
+
+class _SpmmEdgeValuesReduce(torch.autograd.Function):
+    """y[i, slice h] = mean / max over row i's entries e of a[e,h] V[col_e, slice h], differentiable in a and V.
+    mean: the sum's backward on dy / (row entry count); max: dV scattered through the argmax (float atomics), da as a
+    masked per-entry dot"""
+    @staticmethod
+    def forward(ctx, a, V, g, heads, reduce):
+        # a dense [nnz, H]: the kernels (the dV scatter of max among them) read a[e * H + h], whatever the caller's strides
+        a, V = _f32c(a.reshape(g.nnz, heads), "a").contiguous(), _f32c(V, "V")
+        if V.size(1) % heads:
+            raise ValueError(f"V has {V.size(1)} columns, not a multiple of heads = {heads}")
+        y, argmax = _raw_spmm_heads_reduce(g, a, V, heads, reduce)
+        ctx.g, ctx.heads, ctx.reduce = g, heads, reduce
+        ctx.save_for_backward(a, V, argmax)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        a, V, argmax = ctx.saved_tensors
+        g, heads = ctx.g, ctx.heads
+        dy = dy.contiguous()
+        need_a, need_v = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        da = dV = None
+        if ctx.reduce == _lib.MEAN:
+            dym = (dy / g.entry_counts().clamp(min=1.0)[:, None]).contiguous()
+            if need_a:
+                da = _raw_sddmm_dot(g, dym, V, heads, 1.0)
+            if need_v:
+                gt = g._transpose_sorted()
+                dV = _raw_spmm_heads(gt, a[gt.pos.long()].contiguous(), dym, heads)
+            return da, dV, None, None, None
+        if need_a:
+            da = _raw_heads_max_da(g, argmax, dy, V, heads)
+        if need_v:
+            L = lib()
+            dV = torch.zeros_like(V)
+            with torch.cuda.device(V.device):
+                check(L.mp_spmm_heads_max_bwd_f32(ptr(g.col), ptr(a), heads, ptr(argmax), g.num_nodes, V.size(1),
+                                                  ptr(dy), dy.stride(0), ptr(dV), dV.stride(0), _stream()),
+                      "mp_spmm_heads_max_bwd_f32")
+        return da, dV, None, None, None
+
+
+def spmm_edge_values(g, a, V, heads=1, reduce="sum"):
+    """y[i, slice h] = reduce over row i's entries e of a[e,h] V[col_e, slice h]; a [nnz, H], V [n, d] fp32.
+    reduce: "sum" (or "add"), "mean", "max" (argmax ties: the first entry in CSR order)"""
+    if reduce not in _lib.REDUCE:
+        raise ValueError(f"reduce must be one of {sorted(_lib.REDUCE)}, got {reduce!r}")
+    r = _lib.REDUCE[reduce]
+    if r == _lib.SUM:
+        return _SpmmEdgeValues.apply(a, V, g, int(heads))
+    return _SpmmEdgeValuesReduce.apply(a, V, g, int(heads), r)
 
 
 # =========================================================================================

@@ -530,6 +530,31 @@ int mp_spmm_csr_heads_f32(const int32_t* rowptr, const int32_t* col, const float
 int mp_spmm_heads_f32(const int32_t* rowptr, const int32_t* col, const float* a,
                       int64_t N, int32_t heads, const float* V, int64_t ldv,
                       float* Y, int64_t ldy, int32_t d, mp_stream_t stream);
+/* mp_spmm_csr_heads_f32 with a reduction: reduce MP_SUM, MP_MEAN or MP_MAX of the weighted messages
+ * a[e*H+h] * V[col[e], slice h] over each row's entries — the attention layers' propagate with aggr = cfg.gnn.agg
+ * (graphgym/contrib/layer/attconv.py:93-104 add attention, :196-205 mul attention).  The semantics of
+ * mp_spmm_csr_f32: mean divides by the row's entry count, an empty row gives 0, max keeps the first entry in CSR
+ * order among equal candidates and writes its index to argmax [N, d] (row stride d; NULL: not written; -1 where no
+ * entry won; hub pieces are merged in piece order).  heads 1 (one weight per entry) or 2, 4, 8 with d % heads == 0;
+ * other head counts return MP_ERR_UNSUPPORTED (run one launch per head on column slices of mp_spmm_csr_f32).
+ * Workspace: mp_spmm_ws_bytes for this reduce (MAX adds the argmax partials of the hub pieces). */
+int mp_spmm_csr_heads_reduce_f32(const int32_t* rowptr, const int32_t* col, const float* a, int64_t N,
+                                 const int32_t* plan, const int32_t* counts_host, int32_t heads, int reduce,
+                                 const float* V, int64_t ldv, float* Y, int64_t ldy, int32_t d, int32_t* argmax,
+                                 void* ws, size_t ws_bytes, mp_stream_t stream);
+/* backward of the multi-head weighted max into V: dV[col[e], c] += a[e*H + c/(d/H)] * dY[r, c] for e = argmax[r, c]
+ * >= 0 (attconv.py:93-104, :196-205 with aggr 'max').  One launch for all heads; no-return float atomics, so dV
+ * (zeroed by the caller) is not bitwise reproducible.  N >= 2^31: MP_ERR_UNSUPPORTED. */
+int mp_spmm_heads_max_bwd_f32(const int32_t* col, const float* a, int32_t heads, const int32_t* argmax, int64_t N,
+                              int32_t d, const float* dY, int64_t ldy, float* dV, int64_t ldv, mp_stream_t stream);
+/* backward of the multi-head weighted max into the weights, a masked per-entry dot on the entry-balanced kernel of
+ * mp_sddmm_dot_stream_f32: da[e*H+h] = sum over the columns c of head h with argmax[row_e*ldm + c] == e of
+ * dY[row_e, c] * V[col_e, c].  Every da[e*H+h] is written (0 where e won nothing); no atomics, the same bits every
+ * run.  row_of from mp_csr_row_ids.  Head layouts of mp_sddmm_dot_stream_f32 only (MP_ERR_UNSUPPORTED otherwise: call
+ * it per head with heads = 1 on column slices of argmax, dY and V). */
+int mp_spmm_heads_max_da_f32(const int32_t* row_of, const int32_t* col, int64_t nnz, const int32_t* argmax,
+                             int64_t ldm, const float* dY, int64_t ldy, const float* V, int64_t ldv, int32_t d,
+                             int32_t heads, float* da, mp_stream_t stream);
 
 /* ------------------------------------------------------------------ *
  * Ego-net batcher: graphgym/models/transform.py:11-38 *
