@@ -19,7 +19,7 @@
 // LDS at d = 256: 2 x 32 KiB (P) + 2 x 24 KiB (W) + 8 x 4.5 KiB (output tiles) + bias = 149 KiB: one workgroup (two
 // waves per SIMD) per CU.
 //
-// Measured at 10^7 x 256 x 256 (scripts/dbg/x3_ablate.hip, profiles/r02_dense_x3_ablation.txt): 7.0 ms against 9.7 ms
+// Measured at 10^7 x 256 x 256 (ablation builds of round 2, profiles/r02_dense_x3_ablation.txt): 7.0 ms against 9.7 ms
 // for the general kernel of gemm.hip and 9.9 ms for the library's fp32 GEMM.  The MFMAs alone take 4.0 ms and the
 // memory side alone 3.9 ms, but the two overlap only partly: a vector memory instruction holds its wave at issue while
 // the CU's address path is busy (~50 cycles per 1 KiB piece or store with every wave issuing, ~2800 cycles of the
@@ -48,9 +48,7 @@ __device__ __forceinline__ void glds16(const void* gsrc, unsigned char* lds_base
   __builtin_amdgcn_global_load_lds((x3_glb_void*)gsrc, (x3_lds_void*)lds_base, 16, 0, 0);
 }
 
-// ABL: ablation bits for scripts/dbg/x3_ablate.hip only (1 no P loads after the prologue, 2 no W loads, 4 no split,
-// 8 no stores, 16 no barrier, 64 report the shader cycles of workgroup 0 in out[0..1], 128 no MFMAs — timing experiments with wrong results); the library builds ABL = 0.
-template <int NCB, int ABL = 0>
+template <int NCB>
 __global__ __launch_bounds__(X3_THREADS, 1) void dense_x3_kernel(const float* __restrict__ P, int64_t ldp,
                                                                  const unsigned char* __restrict__ Ws,
                                                                  const float* __restrict__ bias, int act,
@@ -67,7 +65,6 @@ __global__ __launch_bounds__(X3_THREADS, 1) void dense_x3_kernel(const float* __
   unsigned char* const Bbuf = lds + 2 * X3_ASTAGE;
 
   const int tid = threadIdx.x, lane = tid & 63, lane_c = lane;
-  const uint64_t x3_c0 = (ABL & 64) ? __builtin_readcyclecounter() : 0;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // scalar: LDS-DMA bases and piece loops stay wave-uniform
   const int S = F >> 4;                      // 16-k steps per row block (even: F % 32 == 0)
   const int T = F >> 5;                      // 32-k stages of P per row block (>= 2)
@@ -121,12 +118,7 @@ __global__ __launch_bounds__(X3_THREADS, 1) void dense_x3_kernel(const float* __
     const x3_f32x4 x0 = *reinterpret_cast<const x3_f32x4*>(A + 16 * (g0 ^ f_sw));
     const x3_f32x4 x1 = *reinterpret_cast<const x3_f32x4*>(A + 16 * ((g0 + 1) ^ f_sw));
     const float xv[8] = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
-    if constexpr (ABL & 4) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) p3[0][i] = p3[1][i] = p3[2][i] = (__bf16)xv[i];
-    } else {
-      split3_bf16(xv, p3[0], p3[1], p3[2]);
-    }
+    split3_bf16(xv, p3[0], p3[1], p3[2]);
   };
   // Epilogue of one 32 x 32 tile of row-block iteration `it`.  C/D layout with the W fragment as the A operand:
   // j = lane & 31 is the row of P, i = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) the output column inside the tile, so
@@ -141,7 +133,6 @@ __global__ __launch_bounds__(X3_THREADS, 1) void dense_x3_kernel(const float* __
   float* const bias_l = reinterpret_cast<float*>(lds + 2 * X3_ASTAGE + 2 * BSTAGE + X3_WAVES * X3_OSTAGE);
   if (tid < d) bias_l[tid] = bias != nullptr ? bias[tid] : 0.f;
   auto flush_tile = [&](int it, int cb) {
-    if ((ABL & 8) && act != 77) return;
     int lane = lane_c;                       // opaque copy: keeps the address arithmetic below out of the loop-invariant
     asm volatile("" : "+v"(lane));           // set, whose ~100 hoisted registers would spill the accumulators
     const int f_h = lane >> 5;
@@ -186,9 +177,12 @@ __global__ __launch_bounds__(X3_THREADS, 1) void dense_x3_kernel(const float* __
 
   int s = 0;                                 // k-step of step n: n % S
   int cur_it = 0;                            // row-block iteration being accumulated
-  uint64_t c_comp = 0, c_wait = 0, c_bar = 0;   // (ABL & 64) per-phase shader cycles of one wave
   for (int n = 0; n < nsteps; ++n) {
-    const uint64_t ca = (ABL & 64) ? __builtin_readcyclecounter() : 0;
+    // Three unused locals, where the removed timing study kept its per-phase stamps.  They emit nothing, but without
+    // them the compiler numbers this loop's variables differently and orders three pairs of independent scalar moves
+    // the other way round: the same work, but not, instruction for instruction, the kernel that was measured.  They go
+    // with the next change that re-measures this kernel.
+    [[maybe_unused]] const uint64_t ca = 0, cc = 0, cd = 0;
     const int s1 = s + 1 == S ? 0 : s + 1;
     // the fragment of step n + 1 (its stage landed by the end of step n - 1), split while the MFMAs run
     bf16x8 p3n[3];
@@ -199,7 +193,7 @@ __global__ __launch_bounds__(X3_THREADS, 1) void dense_x3_kernel(const float* __
     // in this step may stay in flight past the wait below (s_waitcnt vmcnt(N) waits for all but the N youngest vector
     // memory operations — loads, stores and LDS-DMA count together, in issue order: MI355X_MICROARCH.md, cycle constants):
     int allow = 0;
-    if (n + 1 < nsteps && !(ABL & 2)) issue_B(s1, (n + 1) & 1);
+    if (n + 1 < nsteps) issue_B(s1, (n + 1) & 1);
     if (s == 0 && n > 0) {
       // seam: the previous row block's tiles, then restart the accumulators; the stores drain during this step and
       // the next (a wave whose 32 rows are not all inside M issues fewer than 4 NCB stores: it waits for everything)
@@ -211,8 +205,8 @@ __global__ __launch_bounds__(X3_THREADS, 1) void dense_x3_kernel(const float* __
         for (int r = 0; r < 16; ++r) acc[cb][r] = 0.f;
       }
       ++cur_it;
-      allow = (full && !(ABL & 8)) ? 1 : 0;
-    } else if ((n & 1) && pf_it < nloc && !(ABL & 1)) {
+      allow = full ? 1 : 0;
+    } else if ((n & 1) && pf_it < nloc) {
       // the P stage two ahead: its buffer held the stage whose last fragment THIS wave read in step n - 1; waited for
       // at the end of the next, even, step
 #pragma unroll
@@ -233,11 +227,7 @@ __global__ __launch_bounds__(X3_THREADS, 1) void dense_x3_kernel(const float* __
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl)
           w3[pl] = *reinterpret_cast<const bf16x8*>(B + pl * (2 * d * 16) + c * 512);
-        if constexpr (ABL & 128) {           // no MFMAs: keep the operands alive, nothing else
-          asm volatile("" ::"v"(w3[0]), "v"(w3[1]), "v"(w3[2]), "v"(p3[0]), "v"(p3[1]), "v"(p3[2]));
-        } else {
-          mfma6(acc[c], w3, p3);
-        }
+        mfma6(acc[c], w3, p3);
       }
     }
     if (pre) {
@@ -245,30 +235,17 @@ __global__ __launch_bounds__(X3_THREADS, 1) void dense_x3_kernel(const float* __
       for (int pl = 0; pl < 3; ++pl) p3[pl] = p3n[pl];
     }
 
-    const uint64_t cc = (ABL & 64) ? __builtin_readcyclecounter() : 0;
     if (allow == 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     else if (allow == 1) {
       if constexpr (NCB == 8) asm volatile("s_waitcnt vmcnt(32)" ::: "memory");
       else if constexpr (NCB == 4) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     } else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const uint64_t cd = (ABL & 64) ? __builtin_readcyclecounter() : 0;
-    if constexpr (!(ABL & 16)) __builtin_amdgcn_s_barrier();
-    if constexpr ((ABL & 64) != 0) {
-      const uint64_t ce = __builtin_readcyclecounter();
-      c_comp += cc - ca; c_wait += cd - cc; c_bar += ce - cd;
-    }
+    __builtin_amdgcn_s_barrier();
     s = s1;
   }
 #pragma unroll
   for (int cb = 0; cb < NCB; ++cb) flush_tile(cur_it, cb);
-  if constexpr ((ABL & 64) != 0) {           // shader cycles of workgroup 0 / wave 0, for scripts/dbg/x3_ablate.hip
-    if (blockIdx.x == 0 && tid == 0) {
-      uint64_t* o64 = reinterpret_cast<uint64_t*>(out);
-      o64[0] = __builtin_readcyclecounter() - x3_c0;
-      o64[1] = 0; o64[2] = c_comp; o64[3] = c_wait; o64[4] = c_bar; o64[5] = (uint64_t)nsteps;
-    }
-  }
 }
 
 // The same transform with loading and multiplying on DIFFERENT waves (round 3, d = 256).  In the kernel above every wave
@@ -280,12 +257,9 @@ __global__ __launch_bounds__(X3_THREADS, 1) void dense_x3_kernel(const float* __
 // counted vmcnt, and meet the others at the one barrier per 16-k step.  12 waves mean 168 registers: the MFMA waves
 // keep ONE fragment of P (the split of step n + 1 is not computed under the MFMAs of step n; the SIMD's other MFMA
 // wave covers the gap).  7.68 -> 7.14 ms at 10^7 x 256 x 256, 14.2 -> 13.0 ms at F = 512 (in-process order A/B,
-// scripts/bench_dense_x3.py with MP_X3_PC=0 / 1).  Tried on top and dropped: W slices requested TWO steps ahead through a
+// the one-role kernel against this one).  Tried on top and dropped: W slices requested TWO steps ahead through a
 // three-slot ring, paid for with half-tile output images (158 KB of LDS): 7.65 vs 7.92 ms for the one-role kernel on
 // its box — no better; a W slice landing within its step was not the limit.
-#ifndef MP_X3PC_ABL
-#define MP_X3PC_ABL 0   // ablation bits (timing studies, wrong results): 1 loaders idle after the prologue, 2 no MFMAs, 4 no output
-#endif
 constexpr int X3PC_LOADERS = 4;
 constexpr int X3PC_THREADS = 64 * (X3_WAVES + X3PC_LOADERS);
 
@@ -360,8 +334,8 @@ __global__ __launch_bounds__(X3PC_THREADS, 3) void dense_x3_pc_kernel(const floa
       const int s1 = s + 1 == S ? 0 : s + 1;
       // W slice of step n + 1: its buffer was last read in step n - 1, which every wave has left.  P stage (n >> 1) + 1
       // at even n: its slot held the stage whose second half was read in step n - 1; it is first read in step n + 2.
-      const bool more_w = n + 1 < nsteps && !(MP_X3PC_ABL & 1);
-      const bool more_p = !(n & 1) && (n >> 1) + 1 < nstages && !(MP_X3PC_ABL & 1);
+      const bool more_w = n + 1 < nsteps;
+      const bool more_p = !(n & 1) && (n >> 1) + 1 < nstages;
       if (more_w) issue_B(s1, (n + 1) & 1);
       if (more_p) {
         issue_stage((n >> 1) + 1);
@@ -392,7 +366,6 @@ __global__ __launch_bounds__(X3PC_THREADS, 3) void dense_x3_pc_kernel(const floa
   float* const bias_l = reinterpret_cast<float*>(lds + 2 * X3_ASTAGE + 2 * BSTAGE + X3_WAVES * X3_OSTAGE);
   if (tid < d) bias_l[tid] = bias != nullptr ? bias[tid] : 0.f;
   auto flush_tile = [&](int it, int cb) {    // (dense_x3_kernel's epilogue: a 32 x 32 tile through the wave's LDS image)
-    if ((MP_X3PC_ABL & 4) && act != 77) return;
     int lane = lane_c;
     asm volatile("" : "+v"(lane));
     const int f_h = lane >> 5;
@@ -446,11 +419,7 @@ __global__ __launch_bounds__(X3PC_THREADS, 3) void dense_x3_pc_kernel(const floa
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl)
           w3[pl] = *reinterpret_cast<const bf16x8*>(B + pl * (2 * d * 16) + c * 512);
-#if MP_X3PC_ABL & 2
-        asm volatile("" ::"v"(w3[0]), "v"(w3[1]), "v"(w3[2]), "v"(p3[0]), "v"(p3[1]), "v"(p3[2]));
-#else
         mfma6(acc[c], w3, p3);
-#endif
       }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this step's LDS reads are done before the loaders overwrite
@@ -513,12 +482,7 @@ int mp_dense_x3_f32(const float* P, int64_t ldp, const void* W_split, const floa
   switch (d) {
     case 64: hipLaunchKernelGGL(dense_x3_kernel<2>, grid, block, 0, st, P, ldp, Ws, bias, (int)act, out, ldo, M, F); break;
     case 128: hipLaunchKernelGGL(dense_x3_kernel<4>, grid, block, 0, st, P, ldp, Ws, bias, (int)act, out, ldo, M, F); break;
-    default: {
-      const char* e = getenv("MP_X3_PC");                    // MP_X3_PC=0: the one-role kernel (A/B studies), read per call
-      if (e && e[0] == '0') hipLaunchKernelGGL(dense_x3_kernel<8>, grid, block, 0, st, P, ldp, Ws, bias, (int)act, out, ldo, M, F);
-      else hipLaunchKernelGGL(dense_x3_pc_kernel, grid, dim3(X3PC_THREADS), 0, st, P, ldp, Ws, bias, (int)act, out, ldo, M, F);
-      break;
-    }
+    default: hipLaunchKernelGGL(dense_x3_pc_kernel, grid, dim3(X3PC_THREADS), 0, st, P, ldp, Ws, bias, (int)act, out, ldo, M, F); break;
   }
   MP_LAUNCH_CHECK();
   return MP_OK;

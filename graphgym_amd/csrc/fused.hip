@@ -68,25 +68,8 @@ __device__ __forceinline__ float max_raw(float a, float b) {
   asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
   return r;
 }
-// -DMP_FUSED_TIMING: s_memtime stamps of the phases of sampled tiles (one tile in 128), read back with mp_debug_read by
-// scripts/dbg/fused_phases.py — how profiles/r03_fused_phases.json was made.  Not part of the product build.
-#ifdef MP_FUSED_TIMING
-__device__ long long g_dbg[1 << 18];
-#define DBG_T(slot) do { if (dbg_on && lane == 0) g_dbg[dbg_base + wave * 16 + (slot)] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
-// (producer/consumer kernel: workgroups 5, 37, 69, ... stamp their first 1000 items: producer wave 0 in slots 0-3, the
-// first consumer wave in slots 4-7)
-#define PC_T(slot) do { if ((blockIdx.x & 31) == 5 && (blockIdx.x >> 5) < 8 && it < 1000 && lane == 0) \
-  g_dbg[(((blockIdx.x >> 5) * 1000 + it) << 3) + (slot)] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define DBG_T(slot) do {} while (0)
-#define PC_T(slot) do {} while (0)
-#endif
-#ifndef MP_W_RING
-#define MP_W_RING 2    // K groups the W fragments of the 64-row kernel are fetched ahead
-#endif
-#ifndef MP_FUSED_U
-#define MP_FUSED_U 16   // neighbour rows in flight per wave in phase A
-#endif
+constexpr int MP_W_RING = 2;    // K groups the W fragments of the 64-row kernel are fetched ahead
+constexpr int MP_FUSED_U = 16;  // neighbour rows in flight per wave in phase A
 
 // one K half of phase B: acc += T[32 x FH] * W[k0 : k0 + FH, 64 columns of this wave]
 // K is walked in groups of 8: hardware k-slot kk (= lane >> 5) of MFMA j takes k = 8 g + 4 kk + j, so a
@@ -145,11 +128,6 @@ __device__ __forceinline__ void mfma_half_bf16x3(const float (*T)[FH + 4], const
   // loads run one group ahead without a second buffer (a double buffer spills at four waves per SIMD).
   bf16x8 bq[2][3];
   auto fetch = [&](int sp, int g) {
-#if defined(MP_ABL_W_L1)      // (ablation builds: every K group reads group 0 / plane 2 re-reads plane 1)
-    g = 0;
-#elif defined(MP_ABL_W_2P)
-    if (sp == 2) { bq[0][2] = bq[0][1]; bq[1][2] = bq[1][1]; return; }
-#endif
     bq[0][sp] = *reinterpret_cast<const bf16x8*>(w0 + sp * plane + g * gstride);
     bq[1][sp] = *reinterpret_cast<const bf16x8*>(w1 + sp * plane + g * gstride);
   };
@@ -218,11 +196,6 @@ __global__ __launch_bounds__(kBlock, KH == 2 ? 3 : 4) void agg_dense_kernel(Fuse
   for (int tile = blockIdx.x; (int64_t)tile * kTileRows < a.N; tile += gridDim.x) {
   const int R0 = tile * kTileRows;
   const int R1 = min(R0 + kTileRows, a.N);
-#ifdef MP_FUSED_TIMING
-  const bool dbg_on = (tile % 128) == 7 && tile / 128 < 2048;
-  const int dbg_base = (tile / 128) * 64;
-#endif
-  DBG_T(0);
 
   // ---- the wave's run of entries (the same for every K half) ----
   // lane i (<= 32) holds the start of tile row i (rows past the end of the matrix are empty)
@@ -332,9 +305,7 @@ __global__ __launch_bounds__(kBlock, KH == 2 ? 3 : 4) void agg_dense_kernel(Fuse
         *reinterpret_cast<f32x4*>(&T[m][c]) = v;
       }
     }
-    DBG_T(1);
     __syncthreads();   // T initialised (and carry_row / inv_deg / defer_l visible)
-    DBG_T(2);
 
     // ---- phase A: this wave's run of entries, feature columns [k0, k0 + FH) ----
     if (es < ee) {
@@ -390,9 +361,7 @@ __global__ __launch_bounds__(kBlock, KH == 2 ? 3 : 4) void agg_dense_kernel(Fuse
       }
       flush();
     }
-    DBG_T(3);
     __syncthreads();
-    DBG_T(4);
 
     // ---- carries: a row cut by run boundaries gets its later parts in wave order ----
     if (tid < FH) {
@@ -415,8 +384,6 @@ __global__ __launch_bounds__(kBlock, KH == 2 ? 3 : 4) void agg_dense_kernel(Fuse
         }
       }
     }
-
-    DBG_T(5);
     // ---- phase B: [32 x FH] tile x W[k0 : k0 + FH, :] on the matrix cores ----
     if constexpr (KH == 1) {
       for (int cb = 0; cb < a.dout; cb += 64 * kWavesPerBlock) {
@@ -434,9 +401,7 @@ __global__ __launch_bounds__(kBlock, KH == 2 ? 3 : 4) void agg_dense_kernel(Fuse
           const float* __restrict__ wp = a.Wm + (int64_t)(4 * kk) * a.ldw + ccol;
           mfma_half<FH, PF>(T, wp, a.ldw, acc0, acc1, fr, kk);
         }
-        DBG_T(6);
         store_block(acc0, acc1, n0);
-        DBG_T(7);
       }
     } else {
 #pragma unroll
@@ -479,15 +444,6 @@ __device__ __forceinline__ void mfma_rows_bf16x3(const float (*T)[FH + 4], const
   // trip per K group serve all of them (a wave with two blocks, one after the other, waits twice as often).
   bf16x8 bq[NB][2][3];
   auto fetch = [&](int sp, int g) {
-#if defined(MP_ABL_W_L1)      // (ablation builds: every K group reads group 0 / plane 2 re-reads plane 1)
-    g = 0;
-#elif defined(MP_ABL_W_2P)
-    if (sp == 2) {
-#pragma unroll
-      for (int n = 0; n < NB; ++n) { bq[n][0][2] = bq[n][0][1]; bq[n][1][2] = bq[n][1][1]; }
-      return;
-    }
-#endif
 #pragma unroll
     for (int n = 0; n < NB; ++n) {
       bq[n][0][sp] = *reinterpret_cast<const bf16x8*>(w0 + n * bstride + sp * plane + g * gstride);
@@ -562,9 +518,6 @@ __device__ __forceinline__ void mfma_rows_bf16x3_ring(const float (*T)[FH + 4], 
   constexpr int G = FH / 16;
   bf16x8 bq[D + 1][2][3];
   auto fetch = [&](int slot, int g) {
-#if defined(MP_ABL_W_L1)
-    g = 0;
-#endif
 #pragma unroll
     for (int sp = 0; sp < 3; ++sp) {
       bq[slot][0][sp] = *reinterpret_cast<const bf16x8*>(w0 + sp * plane + g * gstride);
@@ -672,8 +625,8 @@ __device__ __forceinline__ void mfma_rows(const float (*T)[FH + 4], const float*
 // product, 17.6 ms without product and store).  TR = 64 uses every W fragment for two 32-row MFMA blocks: half the
 // traffic; its two buffers take 133 KB of LDS — one workgroup per CU, up to 256 registers per wave.  NP = 4 producers
 // are the optimum there (2: 24.6 ms, 4: 20.97, 6: 21.8, 8: 22.0).  NC = 4 consumers (64 output columns each per block of
-// 256) for dout <= 256; NC = 8 for wider outputs of one K half; F = 512 keeps NC = 4 with both column blocks of a wave
-// walking K together (eight consumers would need 12 waves of <= 168 registers and spill).  HAS_S: the self-term form.
+// 256) for dout <= 256; NC = 8 for wider outputs, F = 512 -> 512 included since round 4 (rounds 2-3 kept NC = 4 there with
+// both column blocks of a wave walking K together: eight consumers spilled then; see launch_fused).  HAS_S: the self-term form.
 // AGG_ONLY: no product — the consumers store the aggregated rows (a.P) and nothing else: the aggregation itself on
 // this kernel's structure (mp_agg_rows_tiles_f32 below).
 // HOT (AGG_ONLY): the column indices carry a tag in their sign bit (mp_agg_rows_tiles_hot_f32): a tagged column's row
@@ -827,9 +780,7 @@ void agg_dense_pc_kernel(FusedArgs a, unsigned int* __restrict__ tile_ctr, int32
         role_barrier();   // b0, once: the first tile initialised (the consumers pass it too)
       }
     }
-    int it = 0;
     while (cur_tile >= 0 || prev_tile >= 0) {
-      if (wave == 0) PC_T(0);
       const int R0 = cur_tile * kTileRows;
       const int R1 = min(R0 + kTileRows, a.N);
       const int k0 = cur_kh * FH;
@@ -999,9 +950,7 @@ void agg_dense_pc_kernel(FusedArgs a, unsigned int* __restrict__ tile_ctr, int32
           pre = true;
         }
       }
-      if (wave == 0) PC_T(1);
       role_barrier();   // b1: every producer run is reduced into `buf` (and the consumers are done with buf ^ 1)
-      if (wave == 0) PC_T(2);
 
       if constexpr (has_s) {
         if (nxt_tile >= 0) own_rows_store(nxt_tile, buf ^ 1);
@@ -1015,8 +964,6 @@ void agg_dense_pc_kernel(FusedArgs a, unsigned int* __restrict__ tile_ctr, int32
         }
       }
       role_barrier();   // b2: buffer `buf` complete; next_tile_s published by the consumers
-      if (wave == 0) PC_T(3);
-      ++it;
 
       rp_v = rp1; rp_e = rp_e1; es = es1; ee = ee1; first_rl = first_rl1; cont = cont1; cvF = cv1; wvF = wv1;
       prev_tile = cur_tile; prev_kh = cur_kh;
@@ -1034,7 +981,6 @@ void agg_dense_pc_kernel(FusedArgs a, unsigned int* __restrict__ tile_ctr, int32
   } else {
     // consumer accumulators (KH == 2: live across the two halves of a tile)
     f32x16 acc[KH == 2 ? NCB : 1][RB][2];
-    int it = 0;   // (items seen; used by the timing build only)
 
     // one item of consumer work: (prev_tile, K half PKH) from buffer buf ^ 1.  (Walking the two halves of a tile in
     // straight-line code, the half a compile-time constant, was tried: the allocator does worse, 1.3-3.8 KB of scratch.)
@@ -1127,7 +1073,6 @@ void agg_dense_pc_kernel(FusedArgs a, unsigned int* __restrict__ tile_ctr, int32
           for (int b = 0; b < RB; ++b)
 #pragma unroll
             for (int r = 0; r < 16; ++r) { acc[0][b][0][r] = 0.f; acc[0][b][1][r] = 0.f; }
-#ifndef MP_PC_NO_MFMA
           if constexpr (BF16X3) {
             const __bf16* w0 = a.Wsp + ((int64_t)kk * a.dout + ccol) * 8;
             // (64-row tiles, 4 consumers: 169 of 256 registers — room for fragments two K groups ahead: 21.09 -> 20.93 ms,
@@ -1138,16 +1083,9 @@ void agg_dense_pc_kernel(FusedArgs a, unsigned int* __restrict__ tile_ctr, int32
             const float* __restrict__ wp = a.Wm + (int64_t)(4 * kk) * a.ldw + ccol;
             mfma_rows<FH, PF, RB>(T[pb], wp, a.ldw, acc[0], fr, kk);
           }
-#else
-          acc[0][0][0][0] = T[pb][fr][kk + n0];   // (ablation build: no transform)
-#endif
 #pragma unroll
           for (int b = 0; b < RB; ++b) {
-#ifndef MP_PC_NO_STORE
             store_block(acc[0][b][0], acc[0][b][1], n0, b);
-#else
-            if (acc[0][b][0][0] == 1.2345e-30f) store_block(acc[0][b][0], acc[0][b][1], n0, b);   // (ablation build: no output)
-#endif
           }
         }
       } else {
@@ -1159,22 +1097,14 @@ void agg_dense_pc_kernel(FusedArgs a, unsigned int* __restrict__ tile_ctr, int32
 #pragma unroll
               for (int r = 0; r < 16; ++r) { acc[b][q][0][r] = 0.f; acc[b][q][1][r] = 0.f; }
         }
-#ifdef MP_PC_NO_MFMA
-        if (false) {
-#else
         if constexpr (BF16X3 && NCB > 1) {
-#endif
           // the wave's column blocks walk K together (the host sends only dout = 64 NC NCB here: every block of every
           // wave is inside dout; a per-block path beside this one costs the allocator 146 registers of scratch)
           const int ccol = cw * 64 + 2 * fr;
           const __bf16* w0 = a.Wsp + ((int64_t)(pk0 / 8 + kk) * a.dout + ccol) * 8;
           mfma_rows_bf16x3<FH, RB, NCB>(T[pb], w0, (int64_t)64 * kPcCons * 8, (int64_t)a.dout * 16,
                                         (int64_t)a.dout * a.ldws, acc, fr, kk);
-#ifdef MP_PC_NO_MFMA
-        } else if (a.N < 0) {
-#else
         } else {
-#endif
 #pragma unroll
           for (int b = 0; b < NCB; ++b) {
             const int n0 = b * 64 * kPcCons + cw * 64;
@@ -1196,7 +1126,6 @@ void agg_dense_pc_kernel(FusedArgs a, unsigned int* __restrict__ tile_ctr, int32
             }
           }
         }
-        if (cw == 0) PC_T(5);
         if (PKH == KH - 1) {
 #pragma unroll
           for (int b = 0; b < NCB; ++b) {
@@ -1204,9 +1133,6 @@ void agg_dense_pc_kernel(FusedArgs a, unsigned int* __restrict__ tile_ctr, int32
             if (n0 < a.dout) {
 #pragma unroll
               for (int q = 0; q < RB; ++q) {
-#ifdef MP_PC_NO_STORE
-                if (acc[b][q][0][0] == 1.2345e-30f)
-#endif
                 store_block(acc[b][q][0], acc[b][q][1], n0, q);
               }
             }
@@ -1216,9 +1142,7 @@ void agg_dense_pc_kernel(FusedArgs a, unsigned int* __restrict__ tile_ctr, int32
       }   // !AGG_ONLY
     };
     auto sync_advance = [&]() {
-      if (cw == 0) PC_T(6);
       role_barrier();   // b1: the consumers are done with buf ^ 1
-      if (cw == 0) PC_T(7);
       // the item after `nxt` opens a new tile when `nxt` is a last half: it is drawn here and published by b2
       const bool draw = nxt_tile >= 0 && nxt_kh == KH - 1;
       if (tid == kPcThreads - 1 && draw) next_tile_s = (int)atomicAdd(tile_ctr, 1u);
@@ -1234,13 +1158,11 @@ void agg_dense_pc_kernel(FusedArgs a, unsigned int* __restrict__ tile_ctr, int32
         }
       }
       buf ^= 1;
-      ++it;
     };
     if (cur_tile >= 0) {
       if (has_s) role_barrier();   // b0, once (the producers initialise the first tile's buffer)
       sync_advance();
       while (prev_tile >= 0) {      // (the producers run the same number of items)
-        if (cw == 0) PC_T(4);
         work(prev_kh);
         sync_advance();
       }
@@ -1371,11 +1293,6 @@ static int launch_fused_pc(const FusedArgs& a, hipStream_t st) {
   else return launch_fused_tiles<W, KH, NCB, PF>(a, st);
 }
 
-static int fused_variant() {   // MP_FUSED_VARIANT (studies: scripts/dbg/fused_variants.py), read per launch
-  const char* e = getenv("MP_FUSED_VARIANT");
-  return e ? atoi(e) : 0;
-}
-
 // Dispatch.  F >= 256: tiles of 64 rows, 4 gathering + 4 multiplying waves, one workgroup per CU.  In-process A/B at
 // 10^7 rows, 1.1 x 10^8 entries (profiles/r03_fused_variants.json), out only / aggregated rows kept:
 //   F = 256: one-role kernel 23.7 / 24.6 ms, 32 rows x 4 producers 22.5 / 24.3, 64 x 2 24.6 / 25.9, 64 x 4 20.97 / 22.98,
@@ -1383,17 +1300,8 @@ static int fused_variant() {   // MP_FUSED_VARIANT (studies: scripts/dbg/fused_v
 // Narrower layers keep 32-row tiles: their buffers are small enough for two workgroups per CU either way.
 template <int W, int KH, int NCB, int PF>
 static int launch_fused(const FusedArgs& a, hipStream_t st) {
-  const int v = fused_variant();
-  if (v == 9) return launch_fused_tiles<W, KH, NCB, PF>(a, st);
   if constexpr (W == 4) {
     if constexpr (KH == 1) {
-      if (v == 1) return launch_fused_pc<W, KH, NCB, PF, 32, 4, 4, true>(a, st);
-      if (v == 2) return launch_fused_pc<W, KH, NCB, PF, 64, 8, 4>(a, st);
-      if (v == 4) return launch_fused_pc<W, KH, NCB, PF, 64, 2, 4>(a, st);
-      if (v == 5) return launch_fused_pc<W, KH, NCB, PF, 64, 6, 4>(a, st);
-    }
-    if constexpr (KH == 1) {
-      if (v == 3) return launch_fused_pc<W, KH, 1, PF, 64, 4, 4, true>(a, st);
       if (a.dout > 256 && a.S != nullptr) return launch_fused_tiles<W, KH, NCB, PF>(a, st);   // (no self-term form with 8 consumers)
       // small operators: 32-row tiles (twice the workgroups: 2 x 10^5 rows 0.57 vs 0.71 ms; 10^6 rows 2.13 vs 2.09)
       if (a.N < (1 << 19) && a.dout <= 256) return launch_fused_pc<W, KH, NCB, PF, 32, 4, 4, true>(a, st);
@@ -1403,9 +1311,8 @@ static int launch_fused(const FusedArgs& a, hipStream_t st) {
       // F = 512 -> 512: the accumulators live across the K halves.  Eight multiplying waves with one 64-column block each
       // (152 registers; 168 + 20 B of scratch with the self term) against four with two blocks walking K together
       // (rounds 2-3: the one-block form spilled then): 50.8 vs 51.6 ms, with the self term 52.1 vs 52.7 — round 4, same
-      // process and buffers, same bits (MP_FUSED_VARIANT=7: the four-wave form)
-      if (a.dout == 512 && v != 7) return launch_fused_pc<W, KH, 1, PF, 64, 4, 8, true>(a, st);
-      if (a.dout == 512) return launch_fused_pc<W, KH, 2, PF, 64, 4, 4, true>(a, st);
+      // process and buffers, same bits
+      if (a.dout == 512) return launch_fused_pc<W, KH, 1, PF, 64, 4, 8, true>(a, st);
       if (a.dout > 256) return launch_fused_tiles<W, KH, NCB, PF>(a, st);   // (a ragged second block: the one-role kernel)
       return launch_fused_pc<W, KH, 1, PF, 64, 4, 4, true>(a, st);
     }
@@ -1477,12 +1384,6 @@ static int launch_id_rows(const int32_t* rows, const int32_t* crp, const int32_t
 using namespace mp;
 
 extern "C" {
-
-#ifdef MP_FUSED_TIMING
-int mp_debug_read(void* dst, size_t bytes) {
-  return hipMemcpyFromSymbol(dst, HIP_SYMBOL(mp::g_dbg), bytes) == hipSuccess ? 0 : 4;
-}
-#endif
 
 #ifndef MP_FUSED_HOT_TU
 static int agg_dense_common(const int32_t* rowptr, const int32_t* col, const float* val, int64_t N, int reduce,

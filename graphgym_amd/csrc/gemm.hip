@@ -364,9 +364,7 @@ __global__ __launch_bounds__(kBlock, 3) void dense_wgrad_kernel(const float* __r
 // four and g, y and the masked-gradient output pass through a block ONCE per d tile instead of once per (f, d) tile
 // pair.  The kernel is bound by the issue of its vector memory instructions (section on dense_x3.hip in DESIGN.md):
 // per MFMA this form issues 40 % fewer with the ReLU mask, 25 % fewer without.  72 KiB LDS: two blocks per CU.
-// ABL: ablation bits for scripts/dbg/wgrad_ablate.hip only (1 no global loads after the first tile, 2 no split / LDS
-// stores, 4 no MFMAs, 8 no LDS fragment reads — timing experiments with wrong results); the library builds ABL = 0.
-template <bool RELU, int ABL = 0>
+template <bool RELU>
 __global__ __launch_bounds__(kBlock, 2) void dense_wgrad_wide_kernel(const float* __restrict__ P, int64_t ldp,
                                                                      const float* G, int64_t ldg,
                                                                      const float* __restrict__ Y, int64_t ldy,
@@ -462,7 +460,7 @@ __global__ __launch_bounds__(kBlock, 2) void dense_wgrad_wide_kernel(const float
   __syncthreads();
   for (int64_t t = 0; t < ntiles; ++t) {
     const int buf = (int)(t & 1);
-    if (t + 1 < ntiles && !(ABL & 1)) {
+    if (t + 1 < ntiles) {
       fetch(mb + (t + 1) * BK);
       if (do_bias) tally();
     }
@@ -471,27 +469,17 @@ __global__ __launch_bounds__(kBlock, 2) void dense_wgrad_wide_kernel(const float
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int pl = 0; pl < 3; ++pl) {
-          if constexpr (ABL & 8) as[i][pl] = __builtin_bit_cast(bf16x8, rp[i][0] + rg[0]);
-          else as[i][pl] = tr_read8(Pimg[buf][pl][wave >> 1], (wave & 1) * 64 + i * 32, lane);
-        }
+        for (int pl = 0; pl < 3; ++pl) as[i][pl] = tr_read8(Pimg[buf][pl][wave >> 1], (wave & 1) * 64 + i * 32, lane);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         bf16x8 b3[3];
 #pragma unroll
-        for (int pl = 0; pl < 3; ++pl) {
-          if constexpr (ABL & 8) b3[pl] = __builtin_bit_cast(bf16x8, rg[j & 1] + rp[0][1]);
-          else b3[pl] = tr_read8(Gimg[buf][pl], j * 32, lane);
-        }
-        if constexpr (ABL & 4) {
-          asm volatile("" ::"v"(b3[0]), "v"(b3[1]), "v"(b3[2]), "v"(as[0][0]), "v"(as[1][2]));
-        } else {
+        for (int pl = 0; pl < 3; ++pl) b3[pl] = tr_read8(Gimg[buf][pl], j * 32, lane);
 #pragma unroll
-          for (int i = 0; i < 2; ++i) mfma6(acc[i][j], as[i], b3);
-        }
+        for (int i = 0; i < 2; ++i) mfma6(acc[i][j], as[i], b3);
       }
     }
-    if (t + 1 < ntiles && !(ABL & 2)) stash(buf ^ 1);
+    if (t + 1 < ntiles) stash(buf ^ 1);
     __syncthreads();
   }
   float* slab = slabs + c * (int64_t)F * d;
@@ -530,9 +518,6 @@ __global__ __launch_bounds__(kBlock, 2) void dense_wgrad_wide_kernel(const float
 // it three ways and store the bf16 images — 48 KiB per stage, two stages — one workgroup barrier per tile.  P, g and y
 // are read exactly ONCE (the 256 x 128 tile read P once per d tile: FETCH 30.7 GB for 20.5 GB of operands).  One
 // workgroup per CU and one contiguous range of nodes per workgroup: at most kNumCU slabs, all of the same length.
-#ifndef MP_WPC_ABL
-#define MP_WPC_ABL 0   // ablation bits (timing studies, wrong results): 1 loaders idle, 2 no MFMAs, 16 with 1: loads only
-#endif
 constexpr int WPC_MFMA_WAVES = 8, WPC_LOAD_WAVES = 4;
 constexpr int WPC_THREADS = 64 * (WPC_MFMA_WAVES + WPC_LOAD_WAVES);
 
@@ -656,12 +641,8 @@ __global__ __launch_bounds__(WPC_THREADS, 3) void dense_wgrad_pc_kernel(const fl
       for (int u = 0; u < NSET; ++u) {
         const int64_t t = base + u;
         const int sidx = (u + 1) % NSET;
-#if !(MP_WPC_ABL & 1)
         stash(sidx, t + 1, (int)((t + 1) & 1));
         fetch(sidx, t + 1 + NSET);
-#elif (MP_WPC_ABL & 16)
-        fetch(sidx, t + 1 + NSET);                       // (loads only: no split, no LDS stores)
-#endif
         role_barrier();                                // step t done
       }
     }
@@ -707,12 +688,8 @@ __global__ __launch_bounds__(WPC_THREADS, 3) void dense_wgrad_pc_kernel(const fl
         for (int j = 0; j < 4; ++j) {
           bf16x8 b3[3];
 #pragma unroll
-          for (int pl = 0; pl < 3; ++pl) b3[pl] = tr_read8(Gimg[buf][pl][wd], (MP_WPC_ABL & 4) ? 0 : j * 32, lane);
-#if !(MP_WPC_ABL & 2)
+          for (int pl = 0; pl < 3; ++pl) b3[pl] = tr_read8(Gimg[buf][pl][wd], j * 32, lane);
           mfma6(acc[i][j], as, b3);
-#else
-          asm volatile("" ::"v"(b3[0]), "v"(b3[1]), "v"(b3[2]), "v"(as[0]), "v"(as[1]), "v"(as[2]));
-#endif
           // (one fragment set at a time: hoisting the reads of all four d tiles costs 121 registers of scratch; the
           // SIMD's other MFMA wave covers the LDS latency)
           __builtin_amdgcn_sched_barrier(0);
@@ -996,10 +973,6 @@ static int64_t wgrad_pc_chunk(int64_t M) {
   c = ceil_div(c, (int64_t)BK) * BK;
   return c < 4096 ? 4096 : c;
 }
-static bool wgrad_no_pc() {   // MP_WGRAD_PC=0: the 256 x 128 tile kernel (A/B studies), read per call
-  const char* e = getenv("MP_WGRAD_PC");
-  return e && e[0] == '0';
-}
 
 }  // namespace mp
 
@@ -1102,7 +1075,7 @@ static int wgrad_common(const float* P, int64_t ldp, const float* G, int64_t ldg
     }
     return MP_OK;
   }
-  if (vec && F > 128 && d >= 64 && F % 8 == 0 && d % 8 == 0 && !wgrad_no_pc()) {   // loaders + MFMA waves, the whole gradient per workgroup
+  if (vec && F > 128 && d >= 64 && F % 8 == 0 && d % 8 == 0) {   // loaders + MFMA waves, the whole gradient per workgroup
     const int64_t pc_chunk = wgrad_pc_chunk(M);
     const int64_t n_pc = ceil_div(M, pc_chunk);            // <= n_chunk: the workspace of mp_dense_wgrad_ws_bytes holds it
     float* pc_bias = dbias ? (float*)ws + (size_t)n_pc * F * d : nullptr;

@@ -1,6 +1,6 @@
 """Randomised shapes / degree patterns for mp_agg_dense_f32 and mp_agg_rows_tiles_f32 against a float64 evaluation: run
-boundaries that cut rows, empty tiles, rows past N, rows spanning several waves, F = 64 ... 512, every kernel variant
-(MP_FUSED_VARIANT=1 / 3 / 9 in the environment: 32-row / 64-row producer-consumer, one-role kernel)."""
+boundaries that cut rows, empty tiles, rows past N, rows spanning several waves, F = 64 ... 512: every kernel shape the
+dispatch reaches (32-row / 64-row producer-consumer, one-role kernel)."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
