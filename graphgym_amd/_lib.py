@@ -98,6 +98,9 @@ PROTOTYPES = {
     "mp_spmm_csr_heads_f32": (C.c_int, [_p, _p, _p, _i64, _p, _pi32, _i32, _p, _i64, _p, _i64, _i32, _p, _sz, _p]),
     "mp_spmm_heads_f32": (C.c_int, [_p, _p, _p, _i64, _i32, _p, _i64, _p, _i64, _i32, _p]),
     "mp_spmm_csr_heads_reduce_f32": (C.c_int, [_p, _p, _p, _i64, _p, _pi32, _i32, C.c_int, _p, _i64, _p, _i64, _i32, _p, _p, _sz, _p]),
+    "mp_spmm_csr_edge_f32": (C.c_int, [_p, _p, _p, _p, _i64, _p, _pi32, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _i32, C.c_int,
+                                       _p, _p, _p, _sz, _p]),
+    "mp_spmm_edge_bwd_f32": (C.c_int, [_p, _p, _p, _p, _i64, _i64, C.c_int, _p, _i64, _i32, _p, _i64, _p]),
     "mp_spmm_heads_max_bwd_f32": (C.c_int, [_p, _p, _i32, _p, _i64, _i32, _p, _i64, _p, _i64, _p]),
     "mp_spmm_heads_max_da_f32": (C.c_int, [_p, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _i32, _i32, _p, _p]),
     "mp_ego_expand": (C.c_int, [_p, _p, _i64, _p, _i64, _i32, _i32, _p, _p, _p, _p, _p]),

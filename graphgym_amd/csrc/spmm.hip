@@ -391,6 +391,242 @@ __global__ __launch_bounds__(kBlock) void agg_hub_finalize_kernel(AggArgs<E> a) 
   }
 }
 
+// ---- two-gather aggregation: messages that carry an edge feature (generalconv.py:203-209) ---------------------------
+// y[r] = reduce_e val_e * (X[col_e] + M[eid_e] + T[r]) (+ bias): X = x W_j^T by source, M = edge_feature W_e^T by input
+// edge, T = x W_i^T by destination (msg_direction 'both').  agg_rows_kernel with a second gathered operand: the wave
+// reads 64 col and 64 eid words with one coalesced load each, broadcasts an entry's pair to the scalar unit and issues
+// two coalesced row loads for it, U entries = 2U row loads in flight.  No per-entry tensor of width d is written or read.
+// An inserted self loop (eid < 0) has no M term: its load reads row 0 of M (M holds at least one row) and is dropped, so
+// every entry issues the same two loads and the waits stay counted.  T[r] is loaded once when row r starts.
+struct EdgeArgs {
+  AggArgs<F32> a;
+  const int32_t* eid;
+  const float* M; int64_t ldm;
+  const float* T; int64_t ldt;
+};
+
+template <int W, bool HAS_T>
+__device__ __forceinline__ void edge_message(const float (&x)[W], const float (&m)[W], bool has_m,
+                                             const float (&t)[W], float (&v)[W]) {
+#pragma unroll
+  for (int k = 0; k < W; ++k) {
+    v[k] = x[k] + (has_m ? m[k] : 0.f);
+    if constexpr (HAS_T) v[k] += t[k];
+  }
+}
+
+template <int W, int REDUCE, bool WEIGHTED, bool HAS_T, int U>
+__global__ __launch_bounds__(kBlock) void edge_rows_kernel(EdgeArgs g) {
+  const AggArgs<F32>& a = g.a;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int seg = blockIdx.x * kWavesPerBlock + wave;
+  if (seg >= a.n_seg) return;
+  const int c0 = (blockIdx.y * kWave + lane) * W;
+  const bool lane_on = c0 < a.d;
+  const int c0ld = lane_on ? c0 : 0;
+
+  const int r0 = a.seg_row[seg];
+  int r1 = a.seg_row[seg + 1];
+  if (r0 >= r1) return;
+  const int e0 = a.rowptr[r0];
+  int e1 = a.rowptr[r1];
+  {
+    const int last_start = a.rowptr[r1 - 1];   // a hub row is the last row that starts here; the hub path owns it
+    if (e1 - last_start > a.hub_deg) { r1 -= 1; e1 = last_start; }
+  }
+  if (r0 >= r1) return;
+
+  const float* __restrict__ xlane = a.X + c0ld;
+  const float* __restrict__ mlane = g.M + c0ld;
+
+  int rbase = r0;
+  int rendv = (rbase + lane < r1) ? a.rowptr[rbase + 1 + lane] : INT_MAX;
+  int r = r0;
+  int rstart = e0;
+  int rend = bcast_i(rendv, 0);
+
+  RowAcc<F32, W, REDUCE, false> acc;
+  acc.reset();
+  float t[W];
+#pragma unroll
+  for (int k = 0; k < W; ++k) t[k] = 0.f;
+  auto load_t = [&]() {
+    if constexpr (HAS_T) {
+      if (r < r1) load_vec<W>(g.T + (int64_t)r * g.ldt + c0ld, t);
+    }
+  };
+  load_t();
+
+  auto advance = [&]() {
+    r += 1;
+    rstart = rend;
+    if (r - rbase == kWave) {
+      rbase = r;
+      rendv = (rbase + lane < r1) ? a.rowptr[rbase + 1 + lane] : INT_MAX;
+    }
+    rend = (r < r1) ? bcast_i(rendv, r - rbase) : INT_MAX;
+    load_t();
+  };
+
+  for (int ec = e0; ec < e1; ec += kWave) {
+    const int me = min(ec + lane, e1 - 1);
+    const int cv = a.col[me];
+    const int ev = g.eid[me];
+    const float wv = WEIGHTED ? a.val[me] : 1.f;
+    const int n = min(kWave, e1 - ec);
+    for (int jb = 0; jb < n; jb += U) {
+      float xv[U][W], mv[U][W];
+      int ej[U];
+#pragma unroll
+      for (int j = 0; j < U; ++j) {
+        const int c = bcast_i(cv, jb + j);
+        ej[j] = bcast_i(ev, jb + j);
+        load_vec<W>(xlane + (int64_t)c * a.ldx, xv[j]);
+        load_vec<W>(mlane + (int64_t)max(ej[j], 0) * g.ldm, mv[j]);
+      }
+#pragma unroll
+      for (int j = 0; j < U; ++j) {
+        const int e = ec + jb + j;
+        if (e < e1) {
+          while (e >= rend) {
+            finish_row<F32, W, REDUCE, false, true>(a, r, rend - rstart, acc, c0, c0ld, lane_on);
+            advance();
+          }
+          float v[W];
+          edge_message<W, HAS_T>(xv[j], mv[j], ej[j] >= 0, t, v);
+          acc.add(v, WEIGHTED ? bcast_f(wv, jb + j) : 1.f, false, e);
+        }
+      }
+    }
+  }
+  while (r < r1) {
+    finish_row<F32, W, REDUCE, false, true>(a, r, rend - rstart, acc, c0, c0ld, lane_on);
+    advance();
+  }
+}
+
+// Hub path 1/2 of the two-gather form: one wave reduces one piece of a hub row into the partial buffers that
+// agg_hub_finalize_kernel combines in piece order (T[row] is inside every term, so the partials need no fix-up).
+template <int W, int REDUCE, bool WEIGHTED, bool HAS_T, int U>
+__global__ __launch_bounds__(kBlock) void edge_hub_pieces_kernel(EdgeArgs g) {
+  const AggArgs<F32>& a = g.a;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int c0 = (blockIdx.y * kWave + lane) * W;
+  const bool lane_on = c0 < a.d;
+  const int c0ld = lane_on ? c0 : 0;
+  const float* __restrict__ xlane = a.X + c0ld;
+  const float* __restrict__ mlane = g.M + c0ld;
+  const int n_piece = a.header[PW_NPIECE];
+
+  for (int p = blockIdx.x * kWavesPerBlock + wave; p < n_piece; p += gridDim.x * kWavesPerBlock) {
+    const int h = a.piece_hub[p];
+    const int k = a.piece_k[p];
+    const int row = a.hub_row[h];
+    const int rs = a.rowptr[row];
+    const int re = a.rowptr[row + 1];
+    const int e0 = rs + k * a.piece_edges;
+    const int e1 = min(e0 + a.piece_edges, re);
+
+    float t[W];
+#pragma unroll
+    for (int q = 0; q < W; ++q) t[q] = 0.f;
+    if constexpr (HAS_T) load_vec<W>(g.T + (int64_t)row * g.ldt + c0ld, t);
+
+    RowAcc<F32, W, REDUCE, false> acc;
+    acc.reset();
+    for (int ec = e0; ec < e1; ec += kWave) {
+      const int me = min(ec + lane, e1 - 1);
+      const int cv = a.col[me];
+      const int ev = g.eid[me];
+      const float wv = WEIGHTED ? a.val[me] : 1.f;
+      const int n = min(kWave, e1 - ec);
+      for (int jb = 0; jb < n; jb += U) {
+        float xv[U][W], mv[U][W];
+        int ej[U];
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+          const int c = bcast_i(cv, jb + j);
+          ej[j] = bcast_i(ev, jb + j);
+          load_vec<W>(xlane + (int64_t)c * a.ldx, xv[j]);
+          load_vec<W>(mlane + (int64_t)max(ej[j], 0) * g.ldm, mv[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+          const int e = ec + jb + j;
+          if (e < e1) {
+            float v[W];
+            edge_message<W, HAS_T>(xv[j], mv[j], ej[j] >= 0, t, v);
+            acc.add(v, WEIGHTED ? bcast_f(wv, jb + j) : 1.f, false, e);
+          }
+        }
+      }
+    }
+    if (lane_on) {
+      store_f32<W>(a.part + (int64_t)p * a.d + c0, acc.a);
+      if constexpr (REDUCE == MP_MAX) store_i32<W>(a.part_arg + (int64_t)p * a.d + c0, acc.arg);
+    }
+  }
+}
+
+// Backward of the two-gather form into M, sum / mean: dM[eid_e] = val_e (/ deg) * dY[row_e].  One wave per 64 stored
+// entries (balanced whatever the degrees): the row of the first entry by a binary search over rowptr, later rows by
+// walking it; every entry writes one whole row of dM, an input edge belongs to at most one entry — plain stores.
+__global__ __launch_bounds__(kBlock) void edge_bwd_rows_kernel(const int32_t* __restrict__ rowptr,
+                                                               const int32_t* __restrict__ eid,
+                                                               const float* __restrict__ val, int32_t N, int32_t nnz,
+                                                               int mean, const float* __restrict__ dY, int64_t ldy,
+                                                               int32_t d, float* __restrict__ dM, int64_t ldm) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int64_t n_chunk = ((int64_t)nnz + kWave - 1) / kWave;
+  for (int64_t ch = (int64_t)blockIdx.x * kWavesPerBlock + wave; ch < n_chunk; ch += (int64_t)gridDim.x * kWavesPerBlock) {
+    const int ec = (int)(ch * kWave);
+    const int n = min(kWave, nnz - ec);
+    const int me = min(ec + lane, nnz - 1);
+    const int ev = eid[me];
+    const float wv = val ? val[me] : 1.f;
+    int lo = 0, hi = N;                    // the row r with rowptr[r] <= ec < rowptr[r + 1]
+    while (lo < hi) {
+      const int mid = lo + ((hi - lo) >> 1);
+      if (rowptr[mid + 1] <= ec) lo = mid + 1; else hi = mid;
+    }
+    int r = lo;
+    int rend = rowptr[r + 1];
+    for (int j = 0; j < n; ++j) {
+      const int e = ec + j;
+      while (e >= rend) { r += 1; rend = rowptr[r + 1]; }
+      const int ei = bcast_i(ev, j);
+      if (ei < 0) continue;
+      float w = bcast_f(wv, j);
+      if (mean) w /= (float)(rend - rowptr[r]);
+      const float* __restrict__ g = dY + (int64_t)r * ldy;
+      float* __restrict__ o = dM + (int64_t)ei * ldm;
+      for (int c = lane; c < d; c += kWave) o[c] = w * g[c];
+    }
+  }
+}
+
+// ... max: dM[eid[e], c] = val[e] * dY[r, c] for e = argmax[r, c] >= 0.  One wave per output row, lanes across columns;
+// a column of a row has one winner and an input edge one entry, so every target is written at most once.
+__global__ __launch_bounds__(kBlock) void edge_bwd_max_kernel(const int32_t* __restrict__ eid,
+                                                              const float* __restrict__ val,
+                                                              const int32_t* __restrict__ argmax, int64_t N,
+                                                              const float* __restrict__ dY, int64_t ldy, int32_t d,
+                                                              float* __restrict__ dM, int64_t ldm) {
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  for (int64_t r = (int64_t)blockIdx.x * kWavesPerBlock + wave; r < N; r += (int64_t)gridDim.x * kWavesPerBlock) {
+    for (int c = lane; c < d; c += kWave) {
+      const int e = argmax[r * d + c];
+      if (e < 0) continue;
+      const int ei = eid[e];
+      if (ei >= 0) dM[(int64_t)ei * ldm + c] = (val ? val[e] : 1.f) * dY[r * ldy + c];
+    }
+  }
+}
+
 // ---- plan ---------------------------------------------------------------
 
 // The segmentation's tunables travel with the plan (its header words and counts_host carry them): a segment is a
@@ -561,6 +797,28 @@ static int pick_width(const AggArgs<E>& a) {
   return w;
 }
 
+// the hub arrays of the plan (behind seg_row; counts[3], counts[4] = their capacities) and the partial buffers of the
+// hub pieces inside the caller's workspace (mp_spmm_ws_bytes); a.seg_row, a.d and a.Q are set
+template <class E>
+static void bind_hub(AggArgs<E>& a, const int32_t* counts, int reduce, void* ws) {
+  const int32_t n_seg = counts[0], n_piece = counts[2];
+  a.hub_row = a.hub_base = a.hub_np = a.piece_hub = a.piece_k = nullptr;
+  a.part = a.part2 = nullptr; a.part_arg = nullptr;
+  if (n_piece > 0) {
+    const int32_t cap_hub = counts[3], cap_piece = counts[4];
+    a.hub_row = a.seg_row + (n_seg + 1);
+    a.hub_base = a.hub_row + cap_hub;
+    a.hub_np = a.hub_base + cap_hub;
+    a.piece_hub = a.hub_np + cap_hub;
+    a.piece_k = a.piece_hub + cap_piece;
+    char* w = (char*)ws;
+    const size_t slab = align_up((size_t)n_piece * a.d * 4, 256);
+    a.part = (float*)w; w += slab;
+    if (a.Q) { a.part2 = (float*)w; w += slab; }
+    if (reduce == MP_MAX) { a.part_arg = (int32_t*)w; w += slab; }
+  }
+}
+
 template <class E>
 static int agg_common(const int32_t* rowptr, const int32_t* col, const float* val, int64_t N,
                       const int32_t* plan, const int32_t* counts, const typename E::T* X, int64_t ldx,
@@ -596,22 +854,7 @@ static int agg_common(const int32_t* rowptr, const int32_t* col, const float* va
   a.col_scale = col_scale; a.l2norm = l2norm; a.l2_eps = l2_eps;
   a.argmax = argmax; a.d = d;
   a.head_width = heads > 1 ? d / heads : 0;
-  a.hub_row = a.hub_base = a.hub_np = a.piece_hub = a.piece_k = nullptr;
-  a.part = a.part2 = nullptr; a.part_arg = nullptr;
-  if (n_piece > 0) {
-    // the hub arrays sit behind seg_row; counts[3], counts[4] = their capacities
-    const int32_t cap_hub = counts[3], cap_piece = counts[4];
-    a.hub_row = a.seg_row + (n_seg + 1);
-    a.hub_base = a.hub_row + cap_hub;
-    a.hub_np = a.hub_base + cap_hub;
-    a.piece_hub = a.hub_np + cap_hub;
-    a.piece_k = a.piece_hub + cap_piece;
-    char* w = (char*)ws;
-    const size_t slab = align_up((size_t)n_piece * d * 4, 256);
-    a.part = (float*)w; w += slab;
-    if (Q) { a.part2 = (float*)w; w += slab; }
-    if (reduce == MP_MAX) { a.part_arg = (int32_t*)w; w += slab; }
-  }
+  bind_hub(a, counts, reduce, ws);
 
   const int w = pick_width(a);
   if (l2norm && d > kWave * w) return MP_ERR_UNSUPPORTED;   // the row must sit in one wave
@@ -646,6 +889,45 @@ static int agg_common(const int32_t* rowptr, const int32_t* col, const float* va
     case 2: return dispatch_reduce<E, 2>(a, counts, reduce, st);
     default: return dispatch_reduce<E, 1>(a, counts, reduce, st);
   }
+}
+
+// ---- two-gather form: dispatch ------------------------------------------------------------
+
+template <int W, int REDUCE, bool WEIGHTED, bool HAS_T>
+static int launch_edge(const EdgeArgs& g, const int32_t* counts, hipStream_t st) {
+  constexpr int U = F32::kU<W>;
+  const AggArgs<F32>& a = g.a;
+  const int tiles = (int)ceil_div(a.d, kWave * W);
+  dim3 grid((unsigned)ceil_div(a.n_seg, kWavesPerBlock), (unsigned)tiles);
+  hipLaunchKernelGGL((edge_rows_kernel<W, REDUCE, WEIGHTED, HAS_T, U>), grid, dim3(kBlock), 0, st, g);
+  MP_LAUNCH_CHECK();
+  const int n_hub = counts[1], n_piece = counts[2];
+  if (n_hub > 0) {
+    int pb = (int)ceil_div(n_piece, kWavesPerBlock);
+    if (pb > kNumCU * 8) pb = kNumCU * 8;
+    hipLaunchKernelGGL((edge_hub_pieces_kernel<W, REDUCE, WEIGHTED, HAS_T, U>), dim3(pb, tiles), dim3(kBlock), 0, st, g);
+    MP_LAUNCH_CHECK();
+    int hb = (int)ceil_div(n_hub, kWavesPerBlock);
+    if (hb > kNumCU * 8) hb = kNumCU * 8;
+    hipLaunchKernelGGL((agg_hub_finalize_kernel<F32, W, REDUCE, false>), dim3(hb, tiles), dim3(kBlock), 0, st, a);
+    MP_LAUNCH_CHECK();
+  }
+  return MP_OK;
+}
+
+template <int W>
+static int dispatch_edge(const EdgeArgs& g, const int32_t* counts, int reduce, hipStream_t st) {
+  const bool wt = g.a.val != nullptr, ht = g.T != nullptr;
+#define MP_EDGE(R)                                                                              \
+  return wt ? (ht ? launch_edge<W, R, true, true>(g, counts, st) : launch_edge<W, R, true, false>(g, counts, st))   \
+            : (ht ? launch_edge<W, R, false, true>(g, counts, st) : launch_edge<W, R, false, false>(g, counts, st));
+  switch (reduce) {
+    case MP_SUM: MP_EDGE(MP_SUM)
+    case MP_MEAN: MP_EDGE(MP_MEAN)
+    case MP_MAX: MP_EDGE(MP_MAX)
+  }
+#undef MP_EDGE
+  return MP_ERR_INVALID_ARG;
 }
 
 template <class E>
@@ -801,6 +1083,69 @@ int mp_spmm_heads_max_bwd_f32(const int32_t* col, const float* a, int32_t heads,
   if (blocks > kNumCU * 16) blocks = kNumCU * 16;
   hipLaunchKernelGGL(heads_max_bwd_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), col, a, heads,
                      d / heads, argmax, dY, ldy, N, d, dV, ldv);
+  MP_LAUNCH_CHECK();
+  return MP_OK;
+}
+
+int mp_spmm_csr_edge_f32(const int32_t* rowptr, const int32_t* col, const int32_t* eid, const float* val, int64_t N,
+                         const int32_t* plan, const int32_t* counts_host, const float* X, int64_t ldx, const float* M,
+                         int64_t ldm, const float* T, int64_t ldt, float* Y, int64_t ldy, int32_t d, int reduce,
+                         const float* bias, int32_t* argmax, void* ws, size_t ws_bytes, mp_stream_t stream) {
+  if (!rowptr || !col || !eid || !plan || !counts_host || !X || !M || !Y) return MP_ERR_INVALID_ARG;
+  if (N < 0 || d < 1) return MP_ERR_INVALID_ARG;
+  if (reduce < MP_SUM || reduce > MP_MAX) return MP_ERR_INVALID_ARG;
+  if (ldx < d || ldm < d || ldy < d || (T && ldt < d)) return MP_ERR_INVALID_ARG;
+  if (N >= INT32_MAX) return MP_ERR_UNSUPPORTED;
+  if (N == 0) return MP_OK;
+  if (counts_host[0] < 1) return MP_ERR_INVALID_ARG;
+  size_t need = 0;
+  mp_spmm_ws_bytes(counts_host, d, reduce, 0, &need);
+  if (need > 0 && (!ws || ws_bytes < need)) return MP_ERR_WORKSPACE;
+
+  EdgeArgs g;
+  AggArgs<F32>& a = g.a;
+  a.rowptr = rowptr; a.col = col; a.val = val;
+  a.header = plan;
+  a.seg_row = plan + PW_HEADER_WORDS;
+  a.n_seg = counts_host[0];
+  a.hub_deg = counts_host[6];
+  a.piece_edges = counts_host[7];
+  a.X = X; a.ldx = ldx; a.Y = Y; a.ldy = ldy; a.Q = nullptr; a.ldq = 0;
+  a.S = nullptr; a.lds = 0; a.self_scale = 0.f; a.bias = bias; a.act = MP_ACT_NONE;
+  a.col_scale = nullptr; a.l2norm = 0; a.l2_eps = 0.f;
+  a.argmax = reduce == MP_MAX ? argmax : nullptr; a.d = d; a.head_width = 0;
+  bind_hub(a, counts_host, reduce, ws);
+  g.eid = eid; g.M = M; g.ldm = ldm; g.T = T; g.ldt = T ? ldt : 0;
+
+  int w = pick_width(a);   // then no wider than the two operands only this form reads allow
+  while (w > 1 && (ldm % w || !aligned(M, 4u * w) || (T && (ldt % w || !aligned(T, 4u * w))))) w >>= 1;
+  hipStream_t st = as_stream(stream);
+  switch (w) {
+    case 4: return dispatch_edge<4>(g, counts_host, reduce, st);
+    case 2: return dispatch_edge<2>(g, counts_host, reduce, st);
+    default: return dispatch_edge<1>(g, counts_host, reduce, st);
+  }
+}
+
+int mp_spmm_edge_bwd_f32(const int32_t* rowptr, const int32_t* eid, const float* val, const int32_t* argmax, int64_t N,
+                         int64_t nnz, int reduce, const float* dY, int64_t ldy, int32_t d, float* dM, int64_t ldm,
+                         mp_stream_t stream) {
+  if (!rowptr || !eid || !dY || !dM || N < 0 || nnz < 0 || d < 1) return MP_ERR_INVALID_ARG;
+  if (reduce < MP_SUM || reduce > MP_MAX || (reduce == MP_MAX && !argmax)) return MP_ERR_INVALID_ARG;
+  if (ldy < d || ldm < d) return MP_ERR_INVALID_ARG;
+  if (N >= INT32_MAX || nnz >= INT32_MAX) return MP_ERR_UNSUPPORTED;
+  if (N == 0 || nnz == 0) return MP_OK;
+  if (reduce == MP_MAX) {
+    int64_t blocks = ceil_div(N, kWavesPerBlock);
+    if (blocks > kNumCU * 16) blocks = kNumCU * 16;
+    hipLaunchKernelGGL(edge_bwd_max_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), eid, val,
+                       argmax, N, dY, ldy, d, dM, ldm);
+  } else {
+    int64_t blocks = ceil_div(ceil_div(nnz, kWave), kWavesPerBlock);
+    if (blocks > kNumCU * 16) blocks = kNumCU * 16;
+    hipLaunchKernelGGL(edge_bwd_rows_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), rowptr, eid,
+                       val, (int32_t)N, (int32_t)nnz, reduce == MP_MEAN ? 1 : 0, dY, ldy, d, dM, ldm);
+  }
   MP_LAUNCH_CHECK();
   return MP_OK;
 }

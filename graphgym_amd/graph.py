@@ -228,6 +228,19 @@ class CSRGraph:
             self.__dict__["_edge_op"] = g
         return g
 
+    def input_edge_operator(self, n_edges):
+        """[N, n_edges] operator with one column per INPUT edge (entry e of row r -> column eid[e], same value): reduces
+        per-edge rows [n_edges, k] given in input edge order by destination on the aggregation kernel, without gathering
+        them into entry order first (R = A_edge EF of generaledgeconv's add / mean form, generalconv.py:203-209).  Every
+        stored entry must come from an input edge (eid >= 0)."""
+        cache = self.__dict__.setdefault("_input_edge_op", {})
+        g = cache.get(int(n_edges))
+        if g is None:
+            g = CSRGraph(self.rowptr, self.eid, self.val, None, self.num_nodes, self.nnz, max(int(n_edges), 1))
+            g._plan = self.plan()              # same rowptr, same segmentation
+            cache[int(n_edges)] = g
+        return g
+
     def with_values(self, val):
         """same sparsity pattern (and plan / transpose pattern), other entry values"""
         g = CSRGraph(self.rowptr, self.col, val, self._eid, self.num_nodes, self.nnz, self.num_cols)

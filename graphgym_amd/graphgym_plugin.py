@@ -10,13 +10,16 @@ Importing this module is the whole integration:
   * the built-in keys 'gcnconv', 'sageconv', 'gatconv', 'ginconv', 'generalconv'
     (graphgym/models/layer.py:224-235),
   * the design-space attention keys 'gaddconv', 'gmulconv' (graphgym/contrib/layer/attconv.py:239-240),
-    installed by install_design() — kept apart from ALL_KEYS, the ID-GNN path's keys that install() returns.
+    installed by install_design() — kept apart from ALL_KEYS, the ID-GNN path's keys that install() returns,
+  * the built-in edge-feature keys 'generaledgeconv', 'generalsampleedgeconv' (graphgym/models/layer.py:233-234),
+    installed by install_edge() — a third dictionary, EDGE_KEYS, for the same reason.
 
 ``register_layer`` raises KeyError on a duplicate (register.py:6-10), and built-ins shadow
 registered keys (layer.py:238), so taking over an existing key is done by assignment into the
 dictionaries — ``install(override=True)``, the default.
 """
 from . import attconv as A
+from . import edgeconv as EC
 from . import layers as L
 from . import registry as R
 
@@ -48,6 +51,10 @@ ALL_KEYS = {**ID_KEYS, **TF_KEYS, **BUILTIN_KEYS}
 DESIGN_KEYS = {
     'gaddconv': A.GeneralAddAttConv,
     'gmulconv': A.GeneralMulAttConv,
+}
+EDGE_KEYS = {
+    'generaledgeconv': EC.GeneralEdgeConv,
+    'generalsampleedgeconv': EC.GeneralSampleEdgeConv,
 }
 
 
@@ -90,8 +97,14 @@ def install_design(override=True):
     return _install_keys(DESIGN_KEYS, override)
 
 
+def install_edge(override=True):
+    """Register the edge-feature keys of EDGE_KEYS with install()'s semantics; returns the keys taken."""
+    return _install_keys(EDGE_KEYS, override)
+
+
 installed_keys = install(override=True)
 installed_design_keys = install_design(override=True)
+installed_edge_keys = install_edge(override=True)
 
 
 # ---- the post-ops of GraphGym's layer wrapper on the engine -------------------------------------------------

@@ -5,6 +5,7 @@ C-ABI entry point of libmpengine.so (include/mp_engine.h).
     idgnn_aggregate(g, id, x)    two-branch form of gcn_id (TfgIDLayer.py:510-517)
     index_add_rows(h, id, u)     tensor_scatter_nd_add / index_add_ (K10)
     edge_softmax / sddmm_*       GAT pieces (TfgIDLayer.py:333-355; idconv.py:317-332)
+    spmm_edge(g, x, m, reduce)   aggregation of messages with an edge feature (generalconv.py:203-209)
 """
 import ctypes as C
 import os
@@ -862,6 +863,7 @@ def spmm_edge_values(g, a, V, heads=1, reduce="sum"):
 #   mp::agg_dense_id    act(A (x W + S x W_id) + b)                    gcn_id / GCNIDConvLayer, idconv.py:150-177
 #   mp::dense_fused     act(P W [+ Q W_id] + b)                        the transform after the aggregation
 #   mp::bn_act          BatchNorm1d (training statistics) [+ ReLU]     graphgym/models/layer.py:26-35
+#   mp::spmm_edge       y = reduce_e w_e (x_j + m_e + t_i) + b         GeneralEdgeConvLayer.message, generalconv.py:203-209
 # =========================================================================================
 from typing import Optional, Tuple   # noqa: E402
 
@@ -1405,3 +1407,174 @@ def agg_dense_id(g, x, W, W_id, id_index, bias=None, relu=False, self_scale=0.0)
         return None
     want_P = torch.is_grad_enabled() and W.requires_grad
     return torch.ops.mp.agg_dense_id(x, W, W_id, bias, g.handle, id_index, float(self_scale), bool(relu), want_P)[0]
+
+
+# ---- two-gather aggregation: messages with an edge feature (generalconv.py:203-209) ---------------------------------
+def _edge_f32(t, name):
+    """an operand of spmm_edge: float32 only, rows unit-stride"""
+    _require_hip(t, name)
+    if t.dtype != torch.float32:
+        raise TypeError(f"spmm_edge is float32 only: {name} is {t.dtype} (the edge-feature keys generaledgeconv and "
+                        "generalsampleedgeconv have no bfloat16 or float16 form)")
+    return t if t.dim() == 2 and t.stride(1) == 1 else t.contiguous()
+
+
+def _eid_checked(g, n_edges):
+    """g.eid, after checking once per graph that every stored entry's input position is below n_edges"""
+    if g.eid is None:
+        raise ValueError("spmm_edge needs a graph that knows the input position of its entries (CSRGraph.eid): build it "
+                         "with CSRGraph.from_edge_index")
+    top = g.__dict__.get("_eid_max")
+    if top is None:
+        top = int(g.eid.max().item()) if g.nnz else -1
+        g.__dict__["_eid_max"] = top
+    if n_edges <= top:
+        raise ValueError(f"m has {n_edges} rows, the graph's entries come from input edges up to {top}")
+    return g.eid
+
+
+def _raw_spmm_edge(g, x, m, t=None, bias=None, reduce=_lib.SUM, want_argmax=False, out=None):
+    """one launch of mp_spmm_csr_edge_f32 (+ the hub launches of its plan): y[r] = reduce_e val_e (x[col_e] + m[eid_e] +
+    t[r]) + bias -> (y, argmax [N, d] int32 or None)"""
+    L = lib()
+    N, d = g.num_nodes, x.size(1)
+    eid = _eid_checked(g, m.size(0))
+    if m.size(0) == 0:      # every entry is an inserted loop: the kernel still reads (and drops) row 0
+        m = torch.zeros((1, d), dtype=torch.float32, device=x.device)
+    y = out if out is not None else placement.empty_or_torch((N, d), x.device, reads=(x, m))
+    argmax = torch.empty((N, d), dtype=torch.int32, device=x.device) if want_argmax else None
+    plan, counts, ws, ws_bytes = _plan_ws(g, x.device, d, reduce, False)
+    with torch.cuda.device(x.device):
+        check(L.mp_spmm_csr_edge_f32(ptr(g.rowptr), ptr(g.col), ptr(eid), ptr(g.val), N, ptr(plan), counts, ptr(x),
+                                     x.stride(0), ptr(m), m.stride(0), ptr(t), t.stride(0) if t is not None else 0,
+                                     ptr(y), y.stride(0), d, reduce, ptr(bias), ptr(argmax), ptr(ws), ws_bytes,
+                                     _stream()), "mp_spmm_csr_edge_f32")
+    return y, argmax
+
+
+@custom_op("mp::spmm_edge_raw", mutates_args=(), device_types="cuda")
+def _op_spmm_edge_raw(x: Tensor, m: Tensor, t: Optional[Tensor], bias: Optional[Tensor], graph: int, reduce: int,
+                      want_argmax: bool) -> Tuple[Tensor, Tensor]:
+    g = from_handle(graph)
+    x, m = _edge_f32(x, "x"), _edge_f32(m, "m")
+    t = None if t is None else _edge_f32(t, "t")
+    if x.size(0) != g.num_cols or m.size(1) != x.size(1):
+        raise ValueError(f"x is {tuple(x.shape)}, m is {tuple(m.shape)}: the operator has {g.num_cols} columns and both "
+                         "operands share one width")
+    if t is not None and tuple(t.shape) != (g.num_nodes, x.size(1)):
+        raise ValueError(f"t is {tuple(t.shape)}, expected {(g.num_nodes, x.size(1))}")
+    if bias is not None and bias.dtype != torch.float32:
+        raise TypeError(f"spmm_edge is float32 only: bias is {bias.dtype}")
+    y, argmax = _raw_spmm_edge(g, x, m, t, None if bias is None else bias.contiguous(), reduce, want_argmax)
+    return y, (argmax if argmax is not None else _empty_like_none(x, torch.int32))
+
+
+@_op_spmm_edge_raw.register_fake
+def _(x, m, t, bias, graph, reduce, want_argmax):
+    n = from_handle(graph).num_nodes
+    return x.new_empty((n, x.size(1))), x.new_empty((n, x.size(1)) if want_argmax else (0,), dtype=torch.int32)
+
+
+@custom_op("mp::spmm_edge_bwd_raw", mutates_args=(), device_types="cuda")
+def _op_spmm_edge_bwd_raw(dy: Tensor, argmax: Tensor, graph: int, reduce: int, n_edges: int) -> Tensor:
+    """dm [n_edges, d] of spmm_edge (mp_spmm_edge_bwd_f32): rows of input edges the operator does not hold stay zero"""
+    g = from_handle(graph)
+    dy = dy if dy.stride(-1) == 1 else dy.contiguous()
+    N, d = dy.shape
+    dm = torch.zeros((n_edges, d), dtype=torch.float32, device=dy.device)
+    with torch.cuda.device(dy.device):
+        check(lib().mp_spmm_edge_bwd_f32(ptr(g.rowptr), ptr(g.eid), ptr(g.val), ptr(_none_if_empty(argmax)), N, g.nnz,
+                                         reduce, ptr(dy), dy.stride(0), d, ptr(dm), dm.stride(0), _stream()),
+              "mp_spmm_edge_bwd_f32")
+    return dm
+
+
+@_op_spmm_edge_bwd_raw.register_fake
+def _(dy, argmax, graph, reduce, n_edges):
+    return dy.new_empty((n_edges, dy.size(1)))
+
+
+@custom_op("mp::spmm_edge_dt_raw", mutates_args=(), device_types="cuda")
+def _op_spmm_edge_dt_raw(dy: Tensor, argmax: Tensor, graph: int, reduce: int) -> Tensor:
+    """dt [N, d] of spmm_edge, elementwise: t[r] rides in every entry of row r — (the sum of the row's values [over its
+    entry count for mean]) * dy; max: each column's winner carries it once — val[argmax] * dy, 0 for an empty row"""
+    g = from_handle(graph)
+    if reduce == _lib.MAX:
+        dt = dy if g.val is None else g.val[argmax.clamp(min=0).long()] * dy
+        return torch.where(argmax >= 0, dt, torch.zeros_like(dt))
+    c = g.entry_counts() if g.val is None else g.degree("row")
+    if reduce == _lib.MEAN:
+        c = c / g.entry_counts().clamp(min=1.0)
+    return c[:, None] * dy
+
+
+@_op_spmm_edge_dt_raw.register_fake
+def _(dy, argmax, graph, reduce):
+    return dy.new_empty(dy.shape)
+
+
+@custom_op("mp::spmm_edge", mutates_args=(), device_types="cuda")
+def _op_spmm_edge(x: Tensor, m: Tensor, t: Optional[Tensor], bias: Optional[Tensor], graph: int,
+                  reduce: int) -> Tuple[Tensor, Tensor]:
+    return torch.ops.mp.spmm_edge_raw(x, m, t, bias, graph, reduce, reduce == _lib.MAX)
+
+
+@_op_spmm_edge.register_fake
+def _(x, m, t, bias, graph, reduce):
+    n = from_handle(graph).num_nodes
+    return x.new_empty((n, x.size(1))), x.new_empty((n, x.size(1)) if reduce == _lib.MAX else (0,), dtype=torch.int32)
+
+
+def _spmm_edge_setup(ctx, inputs, output):
+    ctx.set_materialize_grads(False)
+    x, m, t, bias, graph, reduce = inputs
+    ctx.graph, ctx.reduce, ctx.n_edges = graph, reduce, m.size(0)
+    ctx.g_alive = from_handle(graph)
+    ctx.has_t, ctx.has_bias = t is not None, bias is not None
+    ctx.save_for_backward(output[1])
+
+
+def _spmm_edge_backward(ctx, dy, _dargmax):
+    (argmax,) = ctx.saved_tensors
+    if dy is None:
+        return None, None, None, None, None, None
+    dy = dy.contiguous()
+    need = ctx.needs_input_grad
+    is_max = ctx.reduce == _lib.MAX
+    dx = dm = dt = dbias = None
+    if need[0]:     # the operand gathered by source: the plain aggregation's backward
+        if is_max:
+            dx = torch.ops.mp.spmm_max_bwd_raw(dy, argmax, ctx.graph)
+        else:
+            dx = torch.ops.mp.spmm_raw(dy, ctx.graph, 1 if ctx.reduce == _lib.SUM else 2, _lib.SUM, None, 0.0, None,
+                                       False, False)[0]
+    if need[1]:
+        dm = torch.ops.mp.spmm_edge_bwd_raw(dy, argmax, ctx.graph, ctx.reduce, ctx.n_edges)
+    if ctx.has_t and need[2]:
+        dt = torch.ops.mp.spmm_edge_dt_raw(dy, argmax, ctx.graph, ctx.reduce)
+    if ctx.has_bias and need[3]:
+        dbias = dy.sum(0)
+    return dx, dm, dt, dbias, None, None
+
+
+register_autograd("mp::spmm_edge", _spmm_edge_backward, setup_context=_spmm_edge_setup)
+
+
+def spmm_edge(g, x, m, reduce="sum", t=None, bias=None):
+    """y[i] = reduce_{e = (i <- j)} w_e (x[j] + m[eid_e] + t[i]) + bias   (torch.ops.mp.spmm_edge)
+
+    The aggregation of messages that carry an edge feature (GeneralEdgeConvLayer.message, generalconv.py:203-209): x
+    [n, d] is gathered by source, m [E, d] by the entry's position in the input edge_index (g.eid; an inserted self loop
+    has none and gets no m term), t [N, d] is the destination's own term.  One pass, no per-entry tensor.  reduce:
+    'sum'/'add' | 'mean' | 'max' (ties: the first entry in CSR order).  float32 only; the gradient flows to x, m, t and
+    bias, the entry values of g are constants; no float atomics except in dx of 'max' (mp_spmm_max_bwd_f32)."""
+    if reduce not in _lib.REDUCE:
+        raise ValueError(f"reduce must be one of {sorted(_lib.REDUCE)}, got {reduce!r}")
+    for name, v in (("x", x), ("m", m), ("t", t), ("bias", bias)):
+        if v is not None:
+            _require_hip(v, name)
+            if v.dtype != torch.float32:
+                raise TypeError(f"spmm_edge is float32 only: {name} is {v.dtype} (the edge-feature keys generaledgeconv "
+                                "and generalsampleedgeconv have no bfloat16 or float16 form)")
+    _eid_checked(g, m.size(0))
+    return torch.ops.mp.spmm_edge(x, m, t, bias, g.handle, _lib.REDUCE[reduce])[0]

@@ -19,7 +19,11 @@
  *     the int64 `edge_index` tensors GraphGym batches carry;
  *   - row r of a CSR holds the in-edges of DESTINATION node r; `col` holds
  *     SOURCE node ids (SparseAdj: edge_index[0] = row, [1] = col,
- *     sparse_adj.py:50-56; PyG flow source_to_target: edge_index[1] = i).
+ *     sparse_adj.py:50-56; PyG flow source_to_target: edge_index[1] = i);
+ *   - per-edge operands (edge features and what is computed from them: M of
+ *     mp_spmm_csr_edge_f32, generalconv.py:203-209) stay in INPUT edge order;
+ *     a CSR entry finds its row through `eid`, the entry's position in the
+ *     input edge list (-1 - i for a self loop the build inserted).
  */
 #ifndef MP_ENGINE_H
 #define MP_ENGINE_H
@@ -542,6 +546,31 @@ int mp_spmm_csr_heads_reduce_f32(const int32_t* rowptr, const int32_t* col, cons
                                  const int32_t* plan, const int32_t* counts_host, int32_t heads, int reduce,
                                  const float* V, int64_t ldv, float* Y, int64_t ldy, int32_t d, int32_t* argmax,
                                  void* ws, size_t ws_bytes, mp_stream_t stream);
+/* two-gather aggregation of messages that carry an edge feature — GeneralEdgeConvLayer.message, generalconv.py:203-209:
+ * linear_msg(cat(x_i, x_j, edge_feature)) = T[r] + X[col] + M[eid] with X = x W_j^T [n, d], M = edge_feature W_e^T
+ * [E, d] in INPUT edge order and T = x W_i^T [N, d] (msg_direction 'both'; NULL for 'single'):
+ *   Y[r] = reduce_{e in row r} val[e] * (X[col[e]] + M[eid[e]] + T[r]) (+ bias),  reduce MP_SUM / MP_MEAN / MP_MAX.
+ * One pass of the plan kernel with two coalesced row loads per entry: no [nnz, d] message tensor is written or read.
+ * val NULL = ones; T, bias NULL = absent; an entry with eid < 0 (an inserted self loop) has no M term (its load reads
+ * row 0: M must hold at least one row, and more rows than the largest eid).  mean divides by the row's entry count, an
+ * empty row gives 0 (+ bias); max keeps the first entry in CSR order among equal candidates and writes its ENTRY index
+ * to argmax [N, d] (row stride d; NULL: not written; -1 where the row is empty) — the convention of mp_spmm_csr_f32, so
+ * mp_spmm_max_bwd_f32 gives dX.  Rows longer than the plan's hub_deg go through the piece / finalize path.  No atomics:
+ * the same bits every run.  Any d >= 1, leading dimensions >= d (MP_ERR_INVALID_ARG otherwise); N >= 2^31:
+ * MP_ERR_UNSUPPORTED.  Workspace: mp_spmm_ws_bytes(counts_host, d, reduce, 0). */
+int mp_spmm_csr_edge_f32(const int32_t* rowptr, const int32_t* col, const int32_t* eid, const float* val, int64_t N,
+                         const int32_t* plan, const int32_t* counts_host, const float* X, int64_t ldx, const float* M,
+                         int64_t ldm, const float* T, int64_t ldt, float* Y, int64_t ldy, int32_t d, int reduce,
+                         const float* bias, int32_t* argmax, void* ws, size_t ws_bytes, mp_stream_t stream);
+/* backward of mp_spmm_csr_edge_f32 into M (the gradient of the messages of generalconv.py:203-209 with respect to the
+ * edge term), dM [E, d] ZEROED by the caller:
+ *   MP_SUM / MP_MEAN: dM[eid[e]] = val[e] (/ entry count of the row) * dY[row of e];
+ *   MP_MAX:           dM[eid[e], c] = val[e] * dY[r, c] for e = argmax[r, c] >= 0 (argmax row stride d; required).
+ * Entries with eid < 0 write nothing.  An entry belongs to one row and an input edge to at most one entry, so every
+ * target is written at most once: plain stores, the same bits every run.  N or nnz >= 2^31: MP_ERR_UNSUPPORTED. */
+int mp_spmm_edge_bwd_f32(const int32_t* rowptr, const int32_t* eid, const float* val, const int32_t* argmax, int64_t N,
+                         int64_t nnz, int reduce, const float* dY, int64_t ldy, int32_t d, float* dM, int64_t ldm,
+                         mp_stream_t stream);
 /* backward of the multi-head weighted max into V: dV[col[e], c] += a[e*H + c/(d/H)] * dY[r, c] for e = argmax[r, c]
  * >= 0 (attconv.py:93-104, :196-205 with aggr 'max').  One launch for all heads; no-return float atomics, so dV
  * (zeroed by the caller) is not bitwise reproducible.  N >= 2^31: MP_ERR_UNSUPPORTED. */
