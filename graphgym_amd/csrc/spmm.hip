@@ -25,9 +25,14 @@
 // (round to nearest even, v_cvt_pk_bf16_f32).  A lane reads W bf16 (2W bytes, up to 16 B); a 512-byte row (d = 256,
 // W = 4) is half the bytes of the fp32 1 KiB row per load instruction, so Bf16 keeps twice the rows in flight per
 // wave below W = 8.  The partials of the hub path are fp32 for both.
+//
+// What a wave gathers per stored entry is a policy of the two gather kernels (the entry sources below): XRows, the row
+// X[col], or EdgeRows, the rows X[col] and M[eid] of the two-gather form (fp32).  Both walk the entries through
+// MP_WALK_ENTRIES and share the launcher, the argument checks and the width choice.
 #include "common.h"
 #include "vecio.h"
 #include <limits.h>
+#include <type_traits>
 
 namespace mp {
 
@@ -197,13 +202,156 @@ __device__ __forceinline__ void finish_row(const AggArgs<E>& a, int row, int deg
   acc.reset();
 }
 
+// ---- entry sources: what a wave gathers for one stored entry, and how that becomes the entry's fp32 message ---------
+// A source holds the wave's side of the gather: the lane's operand pointers and its index words of the current 64
+// entries.  issue() broadcasts entry j's indices to the scalar unit and issues its row loads into a Rows, returning
+// the index word that consume() needs; consume() turns the two into the message and adds it to the row.  Rows keeps
+// the loaded rows in their raw per-lane form (bf16: packed words, widened in consume — see the file header): U entries
+// are issued before the first is consumed.  start_row() is called when the wave begins a destination row.
+
+// One gather: the message is X[col].  Under BRANCH2 col carries the identity mark in its sign bit.
+template <class E_, int W>
+struct XRows {
+  using E = E_;
+  using Args = AggArgs<E>;
+  static constexpr int kW = W;
+  static constexpr bool kMarks = true;   // the two-branch form exists
+  using Rows = typename E::template Raw<W>;
+  static __host__ __device__ __forceinline__ const AggArgs<E>& agg(const Args& g) { return g; }
+
+  const Args& g;
+  const typename E::T* xlane;
+  int cv;
+
+  __device__ __forceinline__ XRows(const Args& g_, int c0ld) : g(g_), xlane(g_.X + c0ld) {}
+  __device__ __forceinline__ void start_row(int) {}
+  __device__ __forceinline__ void load_index(int me) { cv = g.col[me]; }
+  template <bool BRANCH2>
+  __device__ __forceinline__ void issue(int j, Rows& x, int& cj) const {
+    cj = bcast_i(cv, j);
+    const int c = BRANCH2 ? (cj & 0x7fffffff) : cj;
+    E::template load_raw<W>(xlane + (int64_t)c * g.ldx, x);
+  }
+  template <int REDUCE, bool BRANCH2>
+  __device__ __forceinline__ void consume(const Rows& x, int cj, float w, int e,
+                                          RowAcc<E, W, REDUCE, BRANCH2>& acc) const {
+    acc.add(x, w, BRANCH2 && cj < 0, e);
+  }
+};
+
+// ---- two-gather aggregation: messages that carry an edge feature (generalconv.py:203-209) ---------------------------
+// y[r] = reduce_e val_e * (X[col_e] + M[eid_e] + T[r]) (+ bias): X = x W_j^T by source, M = edge_feature W_e^T by input
+// edge, T = x W_i^T by destination (msg_direction 'both').  The same kernels on a source with a second gathered operand:
+// the wave reads 64 col and 64 eid words with one coalesced load each, broadcasts an entry's pair to the scalar unit and
+// issues two coalesced row loads for it, U entries = 2U row loads in flight.  No per-entry tensor of width d is written or
+// read.  An inserted self loop (eid < 0) has no M term: its load reads row 0 of M (M holds at least one row) and is
+// dropped, so every entry issues the same two loads and the waits stay counted.  T[r] is loaded once when row r starts;
+// on the hub path T[row] is inside every term of a piece, so the partials need no fix-up.  fp32, one head, no marks.
+struct EdgeOperands {
+  const int32_t* eid;
+  const float* M; int64_t ldm;
+  const float* T; int64_t ldt;
+};
+
+struct EdgeArgs {
+  AggArgs<F32> a;
+  EdgeOperands o;
+};
+
+template <int W, bool HAS_T>
+__device__ __forceinline__ void edge_message(const float (&x)[W], const float (&m)[W], bool has_m,
+                                             const float (&t)[W], float (&v)[W]) {
+#pragma unroll
+  for (int k = 0; k < W; ++k) {
+    v[k] = x[k] + (has_m ? m[k] : 0.f);
+    if constexpr (HAS_T) v[k] += t[k];
+  }
+}
+
+template <int W, bool HAS_T>
+struct EdgeRows {
+  using E = F32;
+  using Args = EdgeArgs;
+  static constexpr int kW = W;
+  static constexpr bool kMarks = false;
+  struct Rows { float x[W], m[W]; };
+  static __host__ __device__ __forceinline__ const AggArgs<F32>& agg(const Args& g) { return g.a; }
+
+  const Args& g;
+  const float* xlane;
+  const float* mlane;
+  int c0ld;
+  int cv, ev;
+  float t[W];
+
+  __device__ __forceinline__ EdgeRows(const Args& g_, int c0ld_)
+      : g(g_), xlane(g_.a.X + c0ld_), mlane(g_.o.M + c0ld_), c0ld(c0ld_) {
+#pragma unroll
+    for (int k = 0; k < W; ++k) t[k] = 0.f;
+  }
+  __device__ __forceinline__ void start_row(int r) {
+    if constexpr (HAS_T) load_vec<W>(g.o.T + (int64_t)r * g.o.ldt + c0ld, t);
+  }
+  __device__ __forceinline__ void load_index(int me) { cv = g.a.col[me]; ev = g.o.eid[me]; }
+  template <bool BRANCH2>
+  __device__ __forceinline__ void issue(int j, Rows& xm, int& ej) const {
+    static_assert(!BRANCH2, "the two-gather form has no second branch");
+    const int c = bcast_i(cv, j);
+    ej = bcast_i(ev, j);
+    load_vec<W>(xlane + (int64_t)c * g.a.ldx, xm.x);
+    load_vec<W>(mlane + (int64_t)max(ej, 0) * g.o.ldm, xm.m);
+  }
+  template <int REDUCE>
+  __device__ __forceinline__ void consume(const Rows& xm, int ej, float w, int e,
+                                          RowAcc<F32, W, REDUCE, false>& acc) const {
+    float v[W];
+    edge_message<W, HAS_T>(xm.x, xm.m, ej >= 0, t, v);
+    acc.add(v, w, false, e);
+  }
+};
+
+// The entry walk of every gather kernel: entries [e0, e1) of one wave, 64 at a time.  The wave loads the lanes' index
+// and weight words, then per U entries issues all of their row loads before it consumes them in order; BEFORE runs
+// ahead of entry e's consume (the rows kernel closes finished rows there).  NH > 1: the lane takes the weight of head myh.
+// A macro, expanded in the scope of both kernels (src, a, acc, e0, e1, lane, myh), not a function template: behind a
+// function boundary the compiler orders the loads and allocates registers differently, at the cost of a wave of
+// occupancy in some hub-piece kernels (profiles/r08_spmm_unify.md).
+#define MP_WALK_ENTRIES(...)                                                                    \
+  for (int ec = e0; ec < e1; ec += kWave) {                                                        \
+    const int me = min(ec + lane, e1 - 1);                                                         \
+    src.load_index(me);                                                                            \
+    float wv[NH];                                                                                  \
+    _Pragma("unroll") for (int h = 0; h < NH; ++h) wv[h] = WEIGHTED ? a.val[(int64_t)me * NH + h] : 1.f; \
+    const int n = min(kWave, e1 - ec);                                                             \
+    for (int jb = 0; jb < n; jb += U) {                                                            \
+      typename S::Rows rows[U];                                                                    \
+      int ix[U]; /* two arrays: one struct of both changes the order of the generated loads */     \
+      _Pragma("unroll") for (int j = 0; j < U; ++j) src.template issue<BRANCH2>(jb + j, rows[j], ix[j]); \
+      _Pragma("unroll") for (int j = 0; j < U; ++j) {                                              \
+        const int e = ec + jb + j;                                                                 \
+        if (e < e1) {                                                                              \
+          __VA_ARGS__;                                                                             \
+          float w = WEIGHTED ? bcast_f(wv[0], jb + j) : 1.f;                                       \
+          _Pragma("unroll") for (int h = 1; h < NH; ++h) {                                         \
+            const float wh = bcast_f(wv[h], jb + j);                                               \
+            w = myh == h ? wh : w;                                                                 \
+          }                                                                                        \
+          src.consume(rows[j], ix[j], w, e, acc);                                                  \
+        }                                                                                          \
+      }                                                                                            \
+    }                                                                                              \
+  }
+
 // Main kernel: one wave per segment of whole rows.  Kept from the round-1 variant study: U = 8 rows
 // in flight (fp32; Bf16::kU for bf16), non-temporal stores of Y (-1.2 %); non-temporal index loads, index prefetch
 // and an LDS-staged index tile measured within 0.3 % and are not built.
 // NH > 1 (multi-head attention, TfgIDLayer.py:333-355): every entry carries NH weights (val [nnz, NH]); a lane applies
 // the weight of the head its columns belong to, so all heads aggregate in one launch on full 1 KiB row loads.
-template <class E, int W, int REDUCE, bool WEIGHTED, bool BRANCH2, int U, int NH = 1>
-__global__ __launch_bounds__(kBlock) void agg_rows_kernel(AggArgs<E> a) {
+template <class S, int REDUCE, bool WEIGHTED, bool BRANCH2, int U, int NH = 1>
+__global__ __launch_bounds__(kBlock) void agg_rows_kernel(typename S::Args g) {
+  using E = typename S::E;
+  constexpr int W = S::kW;
+  const AggArgs<E>& a = S::agg(g);
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int seg = blockIdx.x * kWavesPerBlock + wave;
@@ -224,7 +372,7 @@ __global__ __launch_bounds__(kBlock) void agg_rows_kernel(AggArgs<E> a) {
   }
   if (r0 >= r1) return;
 
-  const typename E::T* __restrict__ xlane = a.X + c0ld;
+  S src(g, c0ld);
   const int myh = NH > 1 ? c0ld / a.head_width : 0;
 
   // row ends of up to 64 rows live in one VGPR; the current one is broadcast to an SGPR
@@ -236,8 +384,9 @@ __global__ __launch_bounds__(kBlock) void agg_rows_kernel(AggArgs<E> a) {
 
   RowAcc<E, W, REDUCE, BRANCH2> acc;
   acc.reset();
+  src.start_row(r);
 
-  auto advance = [&]() {
+  auto advance = [&]() {   // move to the next row
     r += 1;
     rstart = rend;
     if (r - rbase == kWave) {
@@ -245,43 +394,13 @@ __global__ __launch_bounds__(kBlock) void agg_rows_kernel(AggArgs<E> a) {
       rendv = (rbase + lane < r1) ? a.rowptr[rbase + 1 + lane] : INT_MAX;
     }
     rend = (r < r1) ? bcast_i(rendv, r - rbase) : INT_MAX;
+    if (r < r1) src.start_row(r);
   };
 
-  for (int ec = e0; ec < e1; ec += kWave) {
-    const int me = min(ec + lane, e1 - 1);
-    const int cv = a.col[me];
-    float wv[NH];
-#pragma unroll
-    for (int h = 0; h < NH; ++h) wv[h] = WEIGHTED ? a.val[(int64_t)me * NH + h] : 1.f;
-    const int n = min(kWave, e1 - ec);
-    for (int jb = 0; jb < n; jb += U) {
-      typename E::template Raw<W> v[U];
-      int cj[U];
-#pragma unroll
-      for (int j = 0; j < U; ++j) {
-        cj[j] = bcast_i(cv, jb + j);
-        const int c = BRANCH2 ? (cj[j] & 0x7fffffff) : cj[j];
-        E::template load_raw<W>(xlane + (int64_t)c * a.ldx, v[j]);
-      }
-#pragma unroll
-      for (int j = 0; j < U; ++j) {
-        const int e = ec + jb + j;
-        if (e < e1) {
-          while (e >= rend) {
-            finish_row<E, W, REDUCE, BRANCH2, true>(a, r, rend - rstart, acc, c0, c0ld, lane_on);
-            advance();
-          }
-          float w = WEIGHTED ? bcast_f(wv[0], jb + j) : 1.f;
-#pragma unroll
-          for (int h = 1; h < NH; ++h) {
-            const float wh = bcast_f(wv[h], jb + j);
-            w = myh == h ? wh : w;
-          }
-          acc.add(v[j], w, BRANCH2 && cj[j] < 0, e);
-        }
-      }
-    }
-  }
+  MP_WALK_ENTRIES(while (e >= rend) {
+    finish_row<E, W, REDUCE, BRANCH2, true>(a, r, rend - rstart, acc, c0, c0ld, lane_on);
+    advance();
+  })
   while (r < r1) {
     finish_row<E, W, REDUCE, BRANCH2, true>(a, r, rend - rstart, acc, c0, c0ld, lane_on);
     advance();
@@ -289,14 +408,17 @@ __global__ __launch_bounds__(kBlock) void agg_rows_kernel(AggArgs<E> a) {
 }
 
 // Hub path 1/2: one wave reduces one piece (<= piece_edges entries) of a hub row.
-template <class E, int W, int REDUCE, bool WEIGHTED, bool BRANCH2, int U, int NH = 1>
-__global__ __launch_bounds__(kBlock) void agg_hub_pieces_kernel(AggArgs<E> a) {
+template <class S, int REDUCE, bool WEIGHTED, bool BRANCH2, int U, int NH = 1>
+__global__ __launch_bounds__(kBlock) void agg_hub_pieces_kernel(typename S::Args g) {
+  using E = typename S::E;
+  constexpr int W = S::kW;
+  const AggArgs<E>& a = S::agg(g);
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int c0 = (blockIdx.y * kWave + lane) * W;
   const bool lane_on = c0 < a.d;
   const int c0ld = lane_on ? c0 : 0;
-  const typename E::T* __restrict__ xlane = a.X + c0ld;
+  S src(g, c0ld);
   const int myh = NH > 1 ? c0ld / a.head_width : 0;
   const int n_piece = a.header[PW_NPIECE];
 
@@ -309,39 +431,10 @@ __global__ __launch_bounds__(kBlock) void agg_hub_pieces_kernel(AggArgs<E> a) {
     const int e0 = rs + k * a.piece_edges;
     const int e1 = min(e0 + a.piece_edges, re);
 
+    src.start_row(row);
     RowAcc<E, W, REDUCE, BRANCH2> acc;
     acc.reset();
-    for (int ec = e0; ec < e1; ec += kWave) {
-      const int me = min(ec + lane, e1 - 1);
-      const int cv = a.col[me];
-      float wv[NH];
-#pragma unroll
-      for (int h = 0; h < NH; ++h) wv[h] = WEIGHTED ? a.val[(int64_t)me * NH + h] : 1.f;
-      const int n = min(kWave, e1 - ec);
-      for (int jb = 0; jb < n; jb += U) {
-        typename E::template Raw<W> v[U];
-        int cj[U];
-#pragma unroll
-        for (int j = 0; j < U; ++j) {
-          cj[j] = bcast_i(cv, jb + j);
-          const int c = BRANCH2 ? (cj[j] & 0x7fffffff) : cj[j];
-          E::template load_raw<W>(xlane + (int64_t)c * a.ldx, v[j]);
-        }
-#pragma unroll
-        for (int j = 0; j < U; ++j) {
-          const int e = ec + jb + j;
-          if (e < e1) {
-            float w = WEIGHTED ? bcast_f(wv[0], jb + j) : 1.f;
-#pragma unroll
-            for (int h = 1; h < NH; ++h) {
-              const float wh = bcast_f(wv[h], jb + j);
-              w = myh == h ? wh : w;
-            }
-            acc.add(v[j], w, BRANCH2 && cj[j] < 0, e);
-          }
-        }
-      }
-    }
+    MP_WALK_ENTRIES((void)0)
     if (lane_on) {
       store_f32<W>(a.part + (int64_t)p * a.d + c0, acc.a);
       if constexpr (BRANCH2) store_f32<W>(a.part2 + (int64_t)p * a.d + c0, acc.b);
@@ -388,185 +481,6 @@ __global__ __launch_bounds__(kBlock) void agg_hub_finalize_kernel(AggArgs<E> a) 
       }
     }
     finish_row<E, W, REDUCE, BRANCH2, E::kNtFinalize>(a, row, deg, acc, c0, c0ld, lane_on);
-  }
-}
-
-// ---- two-gather aggregation: messages that carry an edge feature (generalconv.py:203-209) ---------------------------
-// y[r] = reduce_e val_e * (X[col_e] + M[eid_e] + T[r]) (+ bias): X = x W_j^T by source, M = edge_feature W_e^T by input
-// edge, T = x W_i^T by destination (msg_direction 'both').  agg_rows_kernel with a second gathered operand: the wave
-// reads 64 col and 64 eid words with one coalesced load each, broadcasts an entry's pair to the scalar unit and issues
-// two coalesced row loads for it, U entries = 2U row loads in flight.  No per-entry tensor of width d is written or read.
-// An inserted self loop (eid < 0) has no M term: its load reads row 0 of M (M holds at least one row) and is dropped, so
-// every entry issues the same two loads and the waits stay counted.  T[r] is loaded once when row r starts.
-struct EdgeArgs {
-  AggArgs<F32> a;
-  const int32_t* eid;
-  const float* M; int64_t ldm;
-  const float* T; int64_t ldt;
-};
-
-template <int W, bool HAS_T>
-__device__ __forceinline__ void edge_message(const float (&x)[W], const float (&m)[W], bool has_m,
-                                             const float (&t)[W], float (&v)[W]) {
-#pragma unroll
-  for (int k = 0; k < W; ++k) {
-    v[k] = x[k] + (has_m ? m[k] : 0.f);
-    if constexpr (HAS_T) v[k] += t[k];
-  }
-}
-
-template <int W, int REDUCE, bool WEIGHTED, bool HAS_T, int U>
-__global__ __launch_bounds__(kBlock) void edge_rows_kernel(EdgeArgs g) {
-  const AggArgs<F32>& a = g.a;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int seg = blockIdx.x * kWavesPerBlock + wave;
-  if (seg >= a.n_seg) return;
-  const int c0 = (blockIdx.y * kWave + lane) * W;
-  const bool lane_on = c0 < a.d;
-  const int c0ld = lane_on ? c0 : 0;
-
-  const int r0 = a.seg_row[seg];
-  int r1 = a.seg_row[seg + 1];
-  if (r0 >= r1) return;
-  const int e0 = a.rowptr[r0];
-  int e1 = a.rowptr[r1];
-  {
-    const int last_start = a.rowptr[r1 - 1];   // a hub row is the last row that starts here; the hub path owns it
-    if (e1 - last_start > a.hub_deg) { r1 -= 1; e1 = last_start; }
-  }
-  if (r0 >= r1) return;
-
-  const float* __restrict__ xlane = a.X + c0ld;
-  const float* __restrict__ mlane = g.M + c0ld;
-
-  int rbase = r0;
-  int rendv = (rbase + lane < r1) ? a.rowptr[rbase + 1 + lane] : INT_MAX;
-  int r = r0;
-  int rstart = e0;
-  int rend = bcast_i(rendv, 0);
-
-  RowAcc<F32, W, REDUCE, false> acc;
-  acc.reset();
-  float t[W];
-#pragma unroll
-  for (int k = 0; k < W; ++k) t[k] = 0.f;
-  auto load_t = [&]() {
-    if constexpr (HAS_T) {
-      if (r < r1) load_vec<W>(g.T + (int64_t)r * g.ldt + c0ld, t);
-    }
-  };
-  load_t();
-
-  auto advance = [&]() {
-    r += 1;
-    rstart = rend;
-    if (r - rbase == kWave) {
-      rbase = r;
-      rendv = (rbase + lane < r1) ? a.rowptr[rbase + 1 + lane] : INT_MAX;
-    }
-    rend = (r < r1) ? bcast_i(rendv, r - rbase) : INT_MAX;
-    load_t();
-  };
-
-  for (int ec = e0; ec < e1; ec += kWave) {
-    const int me = min(ec + lane, e1 - 1);
-    const int cv = a.col[me];
-    const int ev = g.eid[me];
-    const float wv = WEIGHTED ? a.val[me] : 1.f;
-    const int n = min(kWave, e1 - ec);
-    for (int jb = 0; jb < n; jb += U) {
-      float xv[U][W], mv[U][W];
-      int ej[U];
-#pragma unroll
-      for (int j = 0; j < U; ++j) {
-        const int c = bcast_i(cv, jb + j);
-        ej[j] = bcast_i(ev, jb + j);
-        load_vec<W>(xlane + (int64_t)c * a.ldx, xv[j]);
-        load_vec<W>(mlane + (int64_t)max(ej[j], 0) * g.ldm, mv[j]);
-      }
-#pragma unroll
-      for (int j = 0; j < U; ++j) {
-        const int e = ec + jb + j;
-        if (e < e1) {
-          while (e >= rend) {
-            finish_row<F32, W, REDUCE, false, true>(a, r, rend - rstart, acc, c0, c0ld, lane_on);
-            advance();
-          }
-          float v[W];
-          edge_message<W, HAS_T>(xv[j], mv[j], ej[j] >= 0, t, v);
-          acc.add(v, WEIGHTED ? bcast_f(wv, jb + j) : 1.f, false, e);
-        }
-      }
-    }
-  }
-  while (r < r1) {
-    finish_row<F32, W, REDUCE, false, true>(a, r, rend - rstart, acc, c0, c0ld, lane_on);
-    advance();
-  }
-}
-
-// Hub path 1/2 of the two-gather form: one wave reduces one piece of a hub row into the partial buffers that
-// agg_hub_finalize_kernel combines in piece order (T[row] is inside every term, so the partials need no fix-up).
-template <int W, int REDUCE, bool WEIGHTED, bool HAS_T, int U>
-__global__ __launch_bounds__(kBlock) void edge_hub_pieces_kernel(EdgeArgs g) {
-  const AggArgs<F32>& a = g.a;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int c0 = (blockIdx.y * kWave + lane) * W;
-  const bool lane_on = c0 < a.d;
-  const int c0ld = lane_on ? c0 : 0;
-  const float* __restrict__ xlane = a.X + c0ld;
-  const float* __restrict__ mlane = g.M + c0ld;
-  const int n_piece = a.header[PW_NPIECE];
-
-  for (int p = blockIdx.x * kWavesPerBlock + wave; p < n_piece; p += gridDim.x * kWavesPerBlock) {
-    const int h = a.piece_hub[p];
-    const int k = a.piece_k[p];
-    const int row = a.hub_row[h];
-    const int rs = a.rowptr[row];
-    const int re = a.rowptr[row + 1];
-    const int e0 = rs + k * a.piece_edges;
-    const int e1 = min(e0 + a.piece_edges, re);
-
-    float t[W];
-#pragma unroll
-    for (int q = 0; q < W; ++q) t[q] = 0.f;
-    if constexpr (HAS_T) load_vec<W>(g.T + (int64_t)row * g.ldt + c0ld, t);
-
-    RowAcc<F32, W, REDUCE, false> acc;
-    acc.reset();
-    for (int ec = e0; ec < e1; ec += kWave) {
-      const int me = min(ec + lane, e1 - 1);
-      const int cv = a.col[me];
-      const int ev = g.eid[me];
-      const float wv = WEIGHTED ? a.val[me] : 1.f;
-      const int n = min(kWave, e1 - ec);
-      for (int jb = 0; jb < n; jb += U) {
-        float xv[U][W], mv[U][W];
-        int ej[U];
-#pragma unroll
-        for (int j = 0; j < U; ++j) {
-          const int c = bcast_i(cv, jb + j);
-          ej[j] = bcast_i(ev, jb + j);
-          load_vec<W>(xlane + (int64_t)c * a.ldx, xv[j]);
-          load_vec<W>(mlane + (int64_t)max(ej[j], 0) * g.ldm, mv[j]);
-        }
-#pragma unroll
-        for (int j = 0; j < U; ++j) {
-          const int e = ec + jb + j;
-          if (e < e1) {
-            float v[W];
-            edge_message<W, HAS_T>(xv[j], mv[j], ej[j] >= 0, t, v);
-            acc.add(v, WEIGHTED ? bcast_f(wv, jb + j) : 1.f, false, e);
-          }
-        }
-      }
-    }
-    if (lane_on) {
-      store_f32<W>(a.part + (int64_t)p * a.d + c0, acc.a);
-      if constexpr (REDUCE == MP_MAX) store_i32<W>(a.part_arg + (int64_t)p * a.d + c0, acc.arg);
-    }
   }
 }
 
@@ -730,19 +644,23 @@ __global__ __launch_bounds__(kBlock) void plan_hub_kernel(const int32_t* __restr
 
 // ---- dispatch -------------------------------------------------------------
 
-template <class E, int W, int REDUCE, bool WEIGHTED, bool BRANCH2, int NH = 1>
-static int launch_agg(const AggArgs<E>& a, const int32_t* counts, hipStream_t st) {
+// the rows kernel over every segment; with hub rows in the plan, their pieces and the finalize pass
+template <class S, int REDUCE, bool WEIGHTED, bool BRANCH2, int NH = 1>
+static int launch_agg(const typename S::Args& g, const int32_t* counts, hipStream_t st) {
+  using E = typename S::E;
+  constexpr int W = S::kW;
   constexpr int U = E::template kU<W>;
+  const AggArgs<E>& a = S::agg(g);
   const int tiles = (int)ceil_div(a.d, kWave * W);
   dim3 grid((unsigned)ceil_div(a.n_seg, kWavesPerBlock), (unsigned)tiles);
-  hipLaunchKernelGGL((agg_rows_kernel<E, W, REDUCE, WEIGHTED, BRANCH2, U, NH>), grid, dim3(kBlock), 0, st, a);
+  hipLaunchKernelGGL((agg_rows_kernel<S, REDUCE, WEIGHTED, BRANCH2, U, NH>), grid, dim3(kBlock), 0, st, g);
   MP_LAUNCH_CHECK();
   const int n_hub = counts[1], n_piece = counts[2];
   if (n_hub > 0) {
     int pb = (int)ceil_div(n_piece, kWavesPerBlock);
     if (pb > kNumCU * 8) pb = kNumCU * 8;
-    hipLaunchKernelGGL((agg_hub_pieces_kernel<E, W, REDUCE, WEIGHTED, BRANCH2, U, NH>), dim3(pb, tiles),
-                       dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL((agg_hub_pieces_kernel<S, REDUCE, WEIGHTED, BRANCH2, U, NH>), dim3(pb, tiles),
+                       dim3(kBlock), 0, st, g);
     MP_LAUNCH_CHECK();
     int hb = (int)ceil_div(n_hub, kWavesPerBlock);
     if (hb > kNumCU * 8) hb = kNumCU * 8;
@@ -753,32 +671,51 @@ static int launch_agg(const AggArgs<E>& a, const int32_t* counts, hipStream_t st
   return MP_OK;
 }
 
-template <class E, int W>
-static int dispatch_reduce(const AggArgs<E>& a, const int32_t* counts, int reduce, hipStream_t st) {
+template <class S>
+static int dispatch_reduce(const typename S::Args& g, const int32_t* counts, int reduce, hipStream_t st) {
+  const auto& a = S::agg(g);
   const bool weighted = a.val != nullptr;
-  if (a.Q != nullptr) {
-    return weighted ? launch_agg<E, W, MP_SUM, true, true>(a, counts, st)
-                    : launch_agg<E, W, MP_SUM, false, true>(a, counts, st);
+  if constexpr (S::kMarks) {
+    if (a.Q != nullptr) {
+      return weighted ? launch_agg<S, MP_SUM, true, true>(g, counts, st)
+                      : launch_agg<S, MP_SUM, false, true>(g, counts, st);
+    }
   }
   switch (reduce) {
     case MP_SUM:
-      return weighted ? launch_agg<E, W, MP_SUM, true, false>(a, counts, st)
-                      : launch_agg<E, W, MP_SUM, false, false>(a, counts, st);
+      return weighted ? launch_agg<S, MP_SUM, true, false>(g, counts, st)
+                      : launch_agg<S, MP_SUM, false, false>(g, counts, st);
     case MP_MEAN:
-      return weighted ? launch_agg<E, W, MP_MEAN, true, false>(a, counts, st)
-                      : launch_agg<E, W, MP_MEAN, false, false>(a, counts, st);
+      return weighted ? launch_agg<S, MP_MEAN, true, false>(g, counts, st)
+                      : launch_agg<S, MP_MEAN, false, false>(g, counts, st);
     case MP_MAX:
-      return weighted ? launch_agg<E, W, MP_MAX, true, false>(a, counts, st)
-                      : launch_agg<E, W, MP_MAX, false, false>(a, counts, st);
+      return weighted ? launch_agg<S, MP_MAX, true, false>(g, counts, st)
+                      : launch_agg<S, MP_MAX, false, false>(g, counts, st);
   }
   return MP_ERR_INVALID_ARG;
+}
+
+// the source: two gathers when the call brings the operands of the two-gather form (fp32 only), else one
+template <class E, int W>
+static int dispatch_source(const AggArgs<E>& a, const EdgeOperands* eo, const int32_t* counts, int reduce,
+                           hipStream_t st) {
+  if (eo) {
+    if constexpr (std::is_same<E, F32>::value) {
+      const EdgeArgs g = {a, *eo};
+      return eo->T ? dispatch_reduce<EdgeRows<W, true>>(g, counts, reduce, st)
+                   : dispatch_reduce<EdgeRows<W, false>>(g, counts, reduce, st);
+    } else {
+      return MP_ERR_UNSUPPORTED;
+    }
+  }
+  return dispatch_reduce<XRows<E, W>>(a, counts, reduce, st);
 }
 
 static bool aligned(const void* p, size_t a) { return p == nullptr || ((uintptr_t)p % a) == 0; }
 
 // widest per-lane vector every operand allows, then no wider than the row needs
 template <class E>
-static int pick_width(const AggArgs<E>& a) {
+static int pick_width(const AggArgs<E>& a, const EdgeOperands* eo) {
   auto ok = [&](int w) {
     const size_t eb = sizeof(typename E::T) * w;   // X, S, Y, Q: one access of w elements per lane
     const size_t fb = 4u * (w < 4 ? w : 4);        // fp32 / int32 operands: vectors of at most 4
@@ -787,6 +724,8 @@ static int pick_width(const AggArgs<E>& a) {
     if (a.ldx % w || a.ldy % w) return false;
     if (a.Q && a.ldq % w) return false;
     if (a.S && a.lds % w) return false;
+    if (eo && (eo->ldm % w || !aligned(eo->M, fb))) return false;
+    if (eo && eo->T && (eo->ldt % w || !aligned(eo->T, fb))) return false;
     return aligned(a.X, eb) && aligned(a.Y, eb) && aligned(a.Q, eb) && aligned(a.S, eb) &&
            aligned(a.bias, fb) && aligned(a.col_scale, fb) && aligned(a.argmax, fb) &&
            aligned(a.part, fb) && aligned(a.part2, fb) && aligned(a.part_arg, fb);
@@ -825,7 +764,8 @@ static int agg_common(const int32_t* rowptr, const int32_t* col, const float* va
                       typename E::T* Y, int64_t ldy, typename E::T* Q, int64_t ldq, int32_t d, int reduce,
                       const typename E::T* S, int64_t lds, float self_scale, const float* bias, int act,
                       int32_t* argmax, void* ws, size_t ws_bytes, hipStream_t st,
-                      const float* col_scale = nullptr, int l2norm = 0, float l2_eps = 1e-12f, int heads = 1) {
+                      const float* col_scale = nullptr, int l2norm = 0, float l2_eps = 1e-12f, int heads = 1,
+                      const EdgeOperands* eo = nullptr) {
   if (!rowptr || !plan || !counts || !X || !Y) return MP_ERR_INVALID_ARG;
   if (N < 0 || d <= 0 || ldx < d || ldy < d) return MP_ERR_INVALID_ARG;
   if (reduce < MP_SUM || reduce > MP_MAX) return MP_ERR_INVALID_ARG;
@@ -856,7 +796,7 @@ static int agg_common(const int32_t* rowptr, const int32_t* col, const float* va
   a.head_width = heads > 1 ? d / heads : 0;
   bind_hub(a, counts, reduce, ws);
 
-  const int w = pick_width(a);
+  const int w = pick_width(a, eo);
   if (l2norm && d > kWave * w) return MP_ERR_UNSUPPORTED;   // the row must sit in one wave
   if constexpr (E::kExtras) {
     if (heads > 1) {
@@ -865,9 +805,9 @@ static int agg_common(const int32_t* rowptr, const int32_t* col, const float* va
       // winning entry per column (argmax, merged across hub pieces in piece order by the finalize kernel)
 #define MP_HEADS_R(WV, R)                                                                      \
       switch (heads) {                                                                         \
-        case 2: return launch_agg<E, WV, R, true, false, 2>(a, counts, st);                   \
-        case 4: return launch_agg<E, WV, R, true, false, 4>(a, counts, st);                   \
-        case 8: return launch_agg<E, WV, R, true, false, 8>(a, counts, st);                   \
+        case 2: return launch_agg<XRows<E, WV>, R, true, false, 2>(a, counts, st);               \
+        case 4: return launch_agg<XRows<E, WV>, R, true, false, 4>(a, counts, st);               \
+        case 8: return launch_agg<XRows<E, WV>, R, true, false, 8>(a, counts, st);               \
         default: return MP_ERR_UNSUPPORTED;                                                    \
       }
 #define MP_HEADS(WV)                                                                           \
@@ -882,52 +822,13 @@ static int agg_common(const int32_t* rowptr, const int32_t* col, const float* va
     }
   }
   if constexpr (E::kMaxW == 8) {
-    if (w == 8) return dispatch_reduce<E, 8>(a, counts, reduce, st);
+    if (w == 8) return dispatch_source<E, 8>(a, eo, counts, reduce, st);
   }
   switch (w) {
-    case 4: return dispatch_reduce<E, 4>(a, counts, reduce, st);
-    case 2: return dispatch_reduce<E, 2>(a, counts, reduce, st);
-    default: return dispatch_reduce<E, 1>(a, counts, reduce, st);
+    case 4: return dispatch_source<E, 4>(a, eo, counts, reduce, st);
+    case 2: return dispatch_source<E, 2>(a, eo, counts, reduce, st);
+    default: return dispatch_source<E, 1>(a, eo, counts, reduce, st);
   }
-}
-
-// ---- two-gather form: dispatch ------------------------------------------------------------
-
-template <int W, int REDUCE, bool WEIGHTED, bool HAS_T>
-static int launch_edge(const EdgeArgs& g, const int32_t* counts, hipStream_t st) {
-  constexpr int U = F32::kU<W>;
-  const AggArgs<F32>& a = g.a;
-  const int tiles = (int)ceil_div(a.d, kWave * W);
-  dim3 grid((unsigned)ceil_div(a.n_seg, kWavesPerBlock), (unsigned)tiles);
-  hipLaunchKernelGGL((edge_rows_kernel<W, REDUCE, WEIGHTED, HAS_T, U>), grid, dim3(kBlock), 0, st, g);
-  MP_LAUNCH_CHECK();
-  const int n_hub = counts[1], n_piece = counts[2];
-  if (n_hub > 0) {
-    int pb = (int)ceil_div(n_piece, kWavesPerBlock);
-    if (pb > kNumCU * 8) pb = kNumCU * 8;
-    hipLaunchKernelGGL((edge_hub_pieces_kernel<W, REDUCE, WEIGHTED, HAS_T, U>), dim3(pb, tiles), dim3(kBlock), 0, st, g);
-    MP_LAUNCH_CHECK();
-    int hb = (int)ceil_div(n_hub, kWavesPerBlock);
-    if (hb > kNumCU * 8) hb = kNumCU * 8;
-    hipLaunchKernelGGL((agg_hub_finalize_kernel<F32, W, REDUCE, false>), dim3(hb, tiles), dim3(kBlock), 0, st, a);
-    MP_LAUNCH_CHECK();
-  }
-  return MP_OK;
-}
-
-template <int W>
-static int dispatch_edge(const EdgeArgs& g, const int32_t* counts, int reduce, hipStream_t st) {
-  const bool wt = g.a.val != nullptr, ht = g.T != nullptr;
-#define MP_EDGE(R)                                                                              \
-  return wt ? (ht ? launch_edge<W, R, true, true>(g, counts, st) : launch_edge<W, R, true, false>(g, counts, st))   \
-            : (ht ? launch_edge<W, R, false, true>(g, counts, st) : launch_edge<W, R, false, false>(g, counts, st));
-  switch (reduce) {
-    case MP_SUM: MP_EDGE(MP_SUM)
-    case MP_MEAN: MP_EDGE(MP_MEAN)
-    case MP_MAX: MP_EDGE(MP_MAX)
-  }
-#undef MP_EDGE
-  return MP_ERR_INVALID_ARG;
 }
 
 template <class E>
@@ -1091,40 +992,11 @@ int mp_spmm_csr_edge_f32(const int32_t* rowptr, const int32_t* col, const int32_
                          const int32_t* plan, const int32_t* counts_host, const float* X, int64_t ldx, const float* M,
                          int64_t ldm, const float* T, int64_t ldt, float* Y, int64_t ldy, int32_t d, int reduce,
                          const float* bias, int32_t* argmax, void* ws, size_t ws_bytes, mp_stream_t stream) {
-  if (!rowptr || !col || !eid || !plan || !counts_host || !X || !M || !Y) return MP_ERR_INVALID_ARG;
-  if (N < 0 || d < 1) return MP_ERR_INVALID_ARG;
-  if (reduce < MP_SUM || reduce > MP_MAX) return MP_ERR_INVALID_ARG;
-  if (ldx < d || ldm < d || ldy < d || (T && ldt < d)) return MP_ERR_INVALID_ARG;
-  if (N >= INT32_MAX) return MP_ERR_UNSUPPORTED;
-  if (N == 0) return MP_OK;
-  if (counts_host[0] < 1) return MP_ERR_INVALID_ARG;
-  size_t need = 0;
-  mp_spmm_ws_bytes(counts_host, d, reduce, 0, &need);
-  if (need > 0 && (!ws || ws_bytes < need)) return MP_ERR_WORKSPACE;
-
-  EdgeArgs g;
-  AggArgs<F32>& a = g.a;
-  a.rowptr = rowptr; a.col = col; a.val = val;
-  a.header = plan;
-  a.seg_row = plan + PW_HEADER_WORDS;
-  a.n_seg = counts_host[0];
-  a.hub_deg = counts_host[6];
-  a.piece_edges = counts_host[7];
-  a.X = X; a.ldx = ldx; a.Y = Y; a.ldy = ldy; a.Q = nullptr; a.ldq = 0;
-  a.S = nullptr; a.lds = 0; a.self_scale = 0.f; a.bias = bias; a.act = MP_ACT_NONE;
-  a.col_scale = nullptr; a.l2norm = 0; a.l2_eps = 0.f;
-  a.argmax = reduce == MP_MAX ? argmax : nullptr; a.d = d; a.head_width = 0;
-  bind_hub(a, counts_host, reduce, ws);
-  g.eid = eid; g.M = M; g.ldm = ldm; g.T = T; g.ldt = T ? ldt : 0;
-
-  int w = pick_width(a);   // then no wider than the two operands only this form reads allow
-  while (w > 1 && (ldm % w || !aligned(M, 4u * w) || (T && (ldt % w || !aligned(T, 4u * w))))) w >>= 1;
-  hipStream_t st = as_stream(stream);
-  switch (w) {
-    case 4: return dispatch_edge<4>(g, counts_host, reduce, st);
-    case 2: return dispatch_edge<2>(g, counts_host, reduce, st);
-    default: return dispatch_edge<1>(g, counts_host, reduce, st);
-  }
+  if (!col || !eid || !M || ldm < d || (T && ldt < d)) return MP_ERR_INVALID_ARG;
+  const EdgeOperands eo = {eid, M, ldm, T, T ? ldt : 0};
+  return agg_common<F32>(rowptr, col, val, N, plan, counts_host, X, ldx, Y, ldy, nullptr, 0, d, reduce, nullptr, 0, 0.f,
+                         bias, MP_ACT_NONE, reduce == MP_MAX ? argmax : nullptr, ws, ws_bytes, as_stream(stream),
+                         nullptr, 0, 1e-12f, 1, &eo);
 }
 
 int mp_spmm_edge_bwd_f32(const int32_t* rowptr, const int32_t* eid, const float* val, const int32_t* argmax, int64_t N,

@@ -220,6 +220,30 @@ def test_inserted_self_loops_carry_no_edge_term(dev, plan, reduce):
     close(Md.grad, both(dm), what=f"loops {reduce} dM", mag=mag_of(lambda c: dm(c, torch.abs)))
 
 
+@pytest.mark.parametrize("reduce", ["sum", "mean", "max"])
+@pytest.mark.parametrize("d", [36, 64, 256])
+@pytest.mark.parametrize("weighted", [True, False], ids=["val", "no_val"])
+def test_without_edge_terms_it_is_the_plain_aggregation(dev, plan, reduce, d, weighted):
+    """every entry with eid < 0, no T, no bias, a one-row M: each message is val * X[col], so the two-gather form gives the
+    bits (and, for max, the winning entries) of the one-gather aggregation on the same operator"""
+    import graphgym_amd as ga
+    from graphgym_amd import ops
+    g0, X, _, _, _, _ = _op_case(dev, d, weighted, seed=d + 1)
+    assert (g0.val is not None) == weighted
+    g = ga.CSRGraph(g0.rowptr, g0.col, g0.val, torch.full_like(g0.eid, -1), g0.num_nodes, g0.nnz)
+    if plan == "hub_plan":
+        assert g.plan()[1][1] > 0 and g.plan()[1][2] > 0
+    Xd = X.to(dev)
+    M = torch.full((1, d), float("nan"), device=dev)              # read and dropped, never added
+    red = ops._lib.REDUCE[reduce]
+    y, win = ops._raw_spmm_edge(g, Xd, M, None, None, red, reduce == "max")
+    assert torch.equal(ops.spmm_edge(g, Xd, M, reduce), y)
+    assert torch.equal(y, ops.spmm(g, Xd, reduce))
+    if reduce == "max":
+        want, want_win = ops._raw_spmm(g, Xd, red, want_argmax=True)
+        assert torch.equal(y, want) and torch.equal(win, want_win)
+
+
 def test_operand_checks(dev):
     import graphgym_amd as ga
     from graphgym_amd import ops
