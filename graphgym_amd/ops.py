@@ -978,9 +978,10 @@ def _(x, graph, id_index):
     return x.new_empty((n, x.size(1))), x.new_empty((n, x.size(1)))
 
 
-def _agg_dense_kernel_ok(g, x, W, S=None):
-    """the one-kernel aggregate -> transform covers these operands (shapes, alignment, row lengths)"""
-    return (agg_dense_supported(g, x, W) and x.dtype == torch.float32
+def _agg_dense_kernel_ok(g, x, W, S=None, reduce=_lib.SUM):
+    """the one-kernel aggregate -> transform covers these operands (shapes, alignment, row lengths; a mean with a self
+    term is outside it: mp_agg_dense_f32 refuses that pair)"""
+    return (agg_dense_supported(g, x, W) and x.dtype == torch.float32 and not (reduce == _lib.MEAN and S is not None)
             and (S is None or (S.stride(0) % 4 == 0 and S.data_ptr() % 16 == 0)))
 
 
@@ -993,7 +994,7 @@ def _op_agg_dense_raw(x: Tensor, W: Tensor, bias: Optional[Tensor], graph: int, 
     x = _agg_in(x, "x")
     Sc = None if S is None else (_f32c(S, "S") if x.dtype == torch.float32 else _agg_in(S, "S"))
     Wd = W.detach()
-    if _agg_dense_kernel_ok(g, x, Wd, Sc):
+    if _agg_dense_kernel_ok(g, x, Wd, Sc, reduce):
         out, P = _raw_agg_dense(g, x, Wd, None if bias is None else bias.detach(), relu, S=Sc,
                                 self_scale=self_scale, want_P=want_P, reduce=reduce)
     else:
