@@ -16,9 +16,10 @@ CSRC = os.path.join(HERE, "csrc")
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(CSRC, "libmpengine.so")
 SOURCES = ["spmm.hip", "fused.hip", "fused_hot.hip", "csr_build.hip", "attn.hip", "ego.hip", "edge.hip", "gemm.hip", "dense_x3.hip", "bn.hip", "util.hip", "probe.hip", "loss.hip"]
-HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "vecio.h"), os.path.join(CSRC, "bf16x3.h"), os.path.join(ROOT, "include", "mp_engine.h")]
+HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "vecio.h"), os.path.join(CSRC, "bf16x3.h"), os.path.join(CSRC, "fused_pc.h"),
+           os.path.join(ROOT, "include", "mp_engine.h")]
 ARCH = "gfx950"
-# per-source flags.  fused_hot.hip (the hot kernels of fused.hip alone): uniform branches stay branches, not structurized
+# per-source flags.  fused_hot.hip (the hot kernels of fused_pc.h alone): uniform branches stay branches, not structurized
 # into two one-sided regions — the gather's per-row choice of cache policy otherwise leaves control-flow paths with zero
 # or two loads, and the wait counting falls back to vmcnt(0) at every consumed row (see the file)
 EXTRA_FLAGS = {"fused_hot.hip": ["-mllvm", "-structurizecfg-skip-uniform-regions=true"]}

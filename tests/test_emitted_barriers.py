@@ -5,7 +5,7 @@ merge, hoist or duplicate a convergent call), so this test reads what was EMITTE
 objects of the built engine, rebuilds each kernel's control-flow graph, finds its loops (strongly connected components)
 and checks, for every instantiation,
 
-    agg_dense_pc_kernel (fused.hip)     two loops with 2 barriers each (b1, b2) — producers and consumers — and outside
+    agg_dense_pc_kernel (fused_pc.h)    two loops with 2 barriers each (b1, b2) — producers and consumers — and outside
                                         them 3 barriers (the prologue's, and b1 + b2 of the consumers' first pass), + 2 with
                                         a self term (b0, once per role)
     dense_wgrad_pc_kernel (gemm.hip)    the MFMA loop with 1 barrier per step, the loaders' loop with NSET (2 with the
@@ -146,9 +146,9 @@ def test_agg_dense_pc_kernel_roles_hold_equal_barrier_counts(tmp_path):
     assert len(ks) >= 40                                         # every instantiation the dispatcher can reach
     seen = set()
     for sym, ins in ks.items():
-        # <W, WEIGHTED, U, KH, NCB, PF, NT_OUT, BF16X3, TR, NP, NC, HAS_S, AGG_ONLY, ...>
+        # <W, WEIGHTED, KH, NCB, PF, BF16X3, TR, NP, NC, HAS_S, AGG_ONLY, ...>
         targs = _template_args(sym, "agg_dense_pc_kernel")
-        has_s = targs[11]
+        has_s = targs[9]
         loops, outside = barriers_by_loop(ins)
         assert loops == [2, 2], (sym, loops, outside)            # b1 + b2 per item in the producers' AND the consumers' loop
         assert outside == 3 + (2 if has_s else 0), (sym, loops, outside)

@@ -371,9 +371,18 @@ def test_id_layers_take_one_launch(dev):
         ops._raw_agg_dense = orig
 
 
-@pytest.mark.parametrize("n,E,F,d,weighted,hubs", [(3000, 40000, 256, 256, True, True), (1000, 9000, 128, 64, False, False),
-                                                    (800, 9000, 512, 512, True, False), (500, 3000, 64, 130, True, False)])
-def test_bf16x3_product_is_fp32_accurate(dev, n, E, F, d, weighted, hubs):
+@pytest.mark.parametrize("n,E,F,d,weighted,hubs,self_scale", [
+    # (the cases without a self term keep the ids they had before the test took one)
+    pytest.param(3000, 40000, 256, 256, True, True, 0.0, id="3000-40000-256-256-True-True"),
+    pytest.param(1000, 9000, 128, 64, False, False, 0.0, id="1000-9000-128-64-False-False"),
+    pytest.param(800, 9000, 512, 512, True, False, 0.0, id="800-9000-512-512-True-False"),
+    pytest.param(500, 3000, 64, 130, True, False, 0.0, id="500-3000-64-130-True-False"),
+    # the one-role kernel's bf16x3 product (the smallest shapes of each branch of launch_fused that falls to it):
+    (600, 7000, 256, 320, True, True, 0.5),        # F = 256, dout > 256 with a self term, a ragged second column block
+    (64, 64, 256, 512, False, False, 2.0),         # ... both column blocks whole
+    (900, 9000, 512, 384, True, True, 0.0),        # F = 512 with a ragged second block
+])
+def test_bf16x3_product_is_fp32_accurate(dev, n, E, F, d, weighted, hubs, self_scale):
     """the one-kernel layer on the bf16 matrix pipe with three-way split operands (six cross terms) against float64, held
     to the same 1e-5 as the exact-fp32 MFMA form, and within a few ulp of that form; weights with a wide dynamic range"""
     import graphgym_amd as ga
@@ -384,18 +393,49 @@ def test_bf16x3_product_is_fp32_accurate(dev, n, E, F, d, weighted, hubs):
     W = torch.randn(F, d, generator=gen) / F ** 0.5 * torch.exp(torch.randn(1, d, generator=gen))
     b = torch.randn(d, generator=gen)
     G = ga.CSRGraph.from_edge_index(ei.to(dev), n, None if w is None else w.to(dev), dst_row=0)
-    exact, _ = ops._raw_agg_dense(G, x.to(dev), W.to(dev), b.to(dev), False, bf16x3=False)
-    split, _ = ops._raw_agg_dense(G, x.to(dev), W.to(dev), b.to(dev), False, bf16x3=True)
-    agg = torch.zeros(n, F, dtype=torch.float64).index_add_(
-        0, ei[0], x.double()[ei[1]] * (w.double().unsqueeze(1) if w is not None else 1.0))
-    ref = agg @ W.double() + b.double()
+    xd = x.to(dev)
+    self_term = dict(S=xd, self_scale=self_scale) if self_scale else {}
+    exact, _ = ops._raw_agg_dense(G, xd, W.to(dev), b.to(dev), False, bf16x3=False, **self_term)
+    split, _ = ops._raw_agg_dense(G, xd, W.to(dev), b.to(dev), False, bf16x3=True, **self_term)
+    ref = _agg_rows64(ei, w, x, n, self_scale) @ W.double() + b.double()
     from _tol import assert_close_rows
     assert_close_rows(split, ref, 1e-5, ref32=exact, what="bf16x3 vs float64")
     e_split = float((split.cpu().double() - ref).abs().max())
     e_exact = float((exact.cpu().double() - ref).abs().max())
     assert e_split <= 4 * e_exact + 1e-7 * float(ref.abs().max()), (e_split, e_exact)
-    split2, _ = ops._raw_agg_dense(G, x.to(dev), W.to(dev), b.to(dev), False, bf16x3=True)
+    split2, _ = ops._raw_agg_dense(G, xd, W.to(dev), b.to(dev), False, bf16x3=True, **self_term)
     assert torch.equal(split, split2)
+
+
+def _agg_rows64(ei, w, x, n, self_scale=0.0):
+    """sum_j w_ij x[j] + self_scale * x[i] in float64 (rows ei[0], sources ei[1]; every stored entry counts)"""
+    agg = torch.zeros(n, x.size(1), dtype=torch.float64).index_add_(
+        0, ei[0], x.double()[ei[1]] * (w.double().unsqueeze(1) if w is not None else 1.0))
+    return agg + self_scale * x.double()
+
+
+def test_bf16x3_mean_keeps_the_aggregated_rows(dev):
+    """reduce = mean with the aggregated rows kept (the MeanGraphSage forward) on the bf16x3 product: P is the rows' mean
+    over their stored entries (rows without entries are zero), out = P W + b, both against float64"""
+    import graphgym_amd as ga
+    from graphgym_amd import ops
+    from graphgym_amd._lib import MEAN
+    from _tol import assert_close_rows
+    n, F, d = 1000, 128, 64
+    ei, w = make_graph(n, 9000, seed=n + F + 11, hubs=True, weighted=True)
+    gen = torch.Generator().manual_seed(4)
+    x = torch.randn(n, F, generator=gen) * torch.exp(torch.randn(n, 1, generator=gen))
+    W = torch.randn(F, d, generator=gen) / F ** 0.5
+    b = torch.randn(d, generator=gen)
+    G = ga.CSRGraph.from_edge_index(ei.to(dev), n, w.to(dev), dst_row=0)
+    exact, P32 = ops._raw_agg_dense(G, x.to(dev), W.to(dev), b.to(dev), False, want_P=True, reduce=MEAN, bf16x3=False)
+    split, P = ops._raw_agg_dense(G, x.to(dev), W.to(dev), b.to(dev), False, want_P=True, reduce=MEAN, bf16x3=True)
+    count = torch.bincount(ei[0], minlength=n).clamp(min=1).double().unsqueeze(1)
+    mean = _agg_rows64(ei, w, x, n) / count
+    assert bool((torch.bincount(ei[0], minlength=n) == 0).any())             # (the graph has rows without entries)
+    assert_close_rows(P, mean, 1e-5, what="mean rows kept, bf16x3")
+    assert torch.equal(P, P32)                                                # the aggregation does not depend on the product
+    assert_close_rows(split, mean @ W.double() + b.double(), 1e-5, ref32=exact, what="mean layer, bf16x3 vs float64")
 
 
 def test_agg_dense_with_a_residual(dev):
