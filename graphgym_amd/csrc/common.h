@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <type_traits>
 #include "../../include/mp_engine.h"
 
 namespace mp {
@@ -55,6 +56,18 @@ static inline hipStream_t as_stream(mp_stream_t s) { return reinterpret_cast<hip
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// runtime booleans -> template arguments: f receives b0 and b1 as std::bool_constant
+template <class Fn>
+static inline void with_bools(bool b0, bool b1, Fn&& f) {
+  if (b0) {
+    if (b1) f(std::true_type{}, std::true_type{});
+    else f(std::true_type{}, std::false_type{});
+  } else {
+    if (b1) f(std::false_type{}, std::true_type{});
+    else f(std::false_type{}, std::false_type{});
+  }
+}
 
 // grid for a flat elementwise / grid-stride kernel: enough blocks to fill the
 // chip (256 CUs x 8 blocks) and no more

@@ -832,18 +832,6 @@ constexpr int kMaxDevPc = 16;
 // library, defined in fused.hip: fused_hot.hip calls this one.)
 int pc_counter(unsigned int** ctr, hipStream_t st);
 
-// runtime booleans -> template arguments: f receives b0 and b1 as std::bool_constant
-template <class Fn>
-static inline void with_bools(bool b0, bool b1, Fn&& f) {
-  if (b0) {
-    if (b1) f(std::true_type{}, std::true_type{});
-    else f(std::true_type{}, std::false_type{});
-  } else {
-    if (b1) f(std::false_type{}, std::true_type{});
-    else f(std::false_type{}, std::false_type{});
-  }
-}
-
 // one producer/consumer launch over N rows in tiles of TR: its zeroed tile counter, its tile count, and a grid of the
 // workgroups the chip holds at once (LDS: 133 KB each at TR = 64, 67 KB at 32), each drawing tiles from the counter
 struct PcLaunch { unsigned int* ctr = nullptr; int32_t n_tiles = 0; dim3 grid; };

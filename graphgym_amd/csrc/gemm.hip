@@ -18,11 +18,11 @@
 
 namespace mp {
 
-constexpr int BM = 128, BK = 16;
+constexpr int BM = 128, BN = 128, BK = 16;
 
-// TN = 32-column MFMA tiles per wave along N: block tile 128 x (64 * TN).  TN = 2 (128 columns, 3 waves per
-// SIMD) is the default; TN = 4 (256 columns: every A row read once at d <= 256) needs 297 registers, runs
-// one wave per SIMD and measured 25 % slower — not built (profiles/r01_dense.log has the measurement).
+// Block tile 128 x 128: two 32-column MFMA tiles per wave along N, 3 waves per SIMD.  Four per wave (256 columns:
+// every A row read once at d <= 256) needs 297 registers, runs one wave per SIMD and measured 25 % slower — not built
+// (profiles/r01_dense.log has the measurement).
 // VEC = operands allow 16-byte loads (F % 8 == 0, d % 4 == 0, aligned rows); otherwise the loaders fall back to
 // guarded scalar loads (any F, d, leading dimension: e.g. Cora's F = 1433) and everything else is unchanged.
 // The split happens ONCE per element, in the thread that stages it into LDS (splitting in the MFMA lanes instead repeats
@@ -50,17 +50,32 @@ __device__ __forceinline__ bf16x8 tr_read8(const unsigned char* plane, int col0,
   const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
   return __builtin_bit_cast(bf16x8, v);
 }
-template <bool DUAL, int TN, bool VEC>
-__global__ __launch_bounds__(kBlock, TN == 2 ? 3 : 1) void dense_fused_kernel(const float* __restrict__ P, int64_t ldp,
-                                                             const float* __restrict__ W,
-                                                             const float* __restrict__ Q, int64_t ldq,
-                                                             const float* __restrict__ Wid,
-                                                             const float* __restrict__ bias, int act,
-                                                             float* __restrict__ out, int64_t ldo, int64_t M,
-                                                             int32_t F, int32_t d) {
-  constexpr int BN = 64 * TN;
-  constexpr int NB4 = BN / 64;           // float4 loads of B per thread per tile
-  static_assert(TN == 2, "the bf16 LDS images below are laid out for a 128-column block tile");
+// eight consecutive floats of a row (two f32x4), split three ways and stored as one 16-byte chunk per split plane:
+// IMG[plane] AT names the chunk, e.g. MP_STASH8(Pimg[buf], [h][off], lo, hi) stores to Pimg[buf][0..2][h][off].
+// (A macro that indexes the image like the code it replaces: as a __device__ function over a plane pointer the kernels
+// come out with another instruction order; profiles/r11_wgrad_once.md.)
+#define MP_STASH8(IMG, AT, lo, hi)                                                                      \
+  do {                                                                                                  \
+    bf16x8 s_[3];                                                                                       \
+    const float v_[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};                       \
+    split3_bf16(v_, s_[0], s_[1], s_[2]);                                                               \
+    _Pragma("unroll") for (int pl_ = 0; pl_ < 3; ++pl_) *reinterpret_cast<bf16x8*>(&IMG[pl_] AT) = s_[pl_]; \
+  } while (0)
+// zero fill of the accumulators f32x16 acc[NI][NJ].  (A macro: as a function the fill reaches the kernel as one block
+// fill rather than element by element, and the kernels come out with another instruction order.)
+#define MP_ZERO_ACC(acc, NI, NJ)                         \
+  _Pragma("unroll") for (int i_ = 0; i_ < (NI); ++i_)    \
+  _Pragma("unroll") for (int j_ = 0; j_ < (NJ); ++j_)    \
+  _Pragma("unroll") for (int r_ = 0; r_ < 16; ++r_) acc[i_][j_][r_] = 0.f
+
+template <bool DUAL, bool VEC>
+__global__ __launch_bounds__(kBlock, 3) void dense_fused_kernel(const float* __restrict__ P, int64_t ldp,
+                                                                const float* __restrict__ W,
+                                                                const float* __restrict__ Q, int64_t ldq,
+                                                                const float* __restrict__ Wid,
+                                                                const float* __restrict__ bias, int act,
+                                                                float* __restrict__ out, int64_t ldo, int64_t M,
+                                                                int32_t F, int32_t d) {
   // bf16x3 images (three split planes each): A [128 rows][16 k] k-contiguous (a lane's operand is one 16-byte read);
   // B [16 k][128 columns] row-major, chunk-swizzled, consumed through transposed reads
   __shared__ __attribute__((aligned(16))) unsigned char Aimg[2][3][BM * 32];
@@ -71,7 +86,7 @@ __global__ __launch_bounds__(kBlock, TN == 2 ? 3 : 1) void dense_fused_kernel(co
   const int wm = wave >> 1, wn = wave & 1;
   // column blocks of one row block are neighbours in dispatch order: the second reader of an A tile
   // finds it in the Infinity Cache instead of HBM
-  const int ncb = (d + BN - 1) / BN;   // (BN declared below is a compile-time constant of this instantiation)
+  const int ncb = (d + BN - 1) / BN;
   const int64_t m0 = (int64_t)(blockIdx.x / ncb) * BM;
   const int n0 = (int)(blockIdx.x % ncb) * BN;
 
@@ -79,12 +94,12 @@ __global__ __launch_bounds__(kBlock, TN == 2 ? 3 : 1) void dense_fused_kernel(co
   const int a_row = tid >> 1;            // 0..127
   const int a_k = (tid & 1) * 8;         // 0 or 8
   const int b_k = tid >> 4;              // 0..15
-  const int b_n = (tid & 15) * (4 * NB4);  // first of this thread's 4*NB4 consecutive columns
+  const int b_n = (tid & 15) * 8;        // first of this thread's 8 consecutive columns
   const int64_t g_row = m0 + a_row;
   const bool row_ok = g_row < M;
   const int KT = DUAL ? 2 * F : F;
 
-  f32x4 ra[2], rb[NB4];
+  f32x4 ra[2], rb[2];
   auto fetch = [&](int kt) {
     const f32x4 z = {0.f, 0.f, 0.f, 0.f};
     const int k = kt + a_k;
@@ -100,7 +115,7 @@ __global__ __launch_bounds__(kBlock, TN == 2 ? 3 : 1) void dense_fused_kernel(co
       const bool second_b = DUAL && kb >= F;
       const float* wsrc = (second_b ? Wid + (int64_t)(kb - F) * d : W + (int64_t)kb * d) + n0 + b_n;
 #pragma unroll
-      for (int q = 0; q < NB4; ++q)
+      for (int q = 0; q < 2; ++q)
         rb[q] = (kb < KT && n0 + b_n + 4 * q < d) ? *reinterpret_cast<const f32x4*>(wsrc + 4 * q) : z;
     } else {
 #pragma unroll
@@ -113,7 +128,7 @@ __global__ __launch_bounds__(kBlock, TN == 2 ? 3 : 1) void dense_fused_kernel(co
       const bool second_b = DUAL && kb >= F;
       const float* wrow = second_b ? Wid + (int64_t)(kb - F) * d : W + (int64_t)kb * d;
 #pragma unroll
-      for (int q = 0; q < NB4; ++q)
+      for (int q = 0; q < 2; ++q)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int nn = n0 + b_n + 4 * q + i;
@@ -122,27 +137,12 @@ __global__ __launch_bounds__(kBlock, TN == 2 ? 3 : 1) void dense_fused_kernel(co
     }
   };
   auto stash = [&](int buf) {
-    const float av[8] = {ra[0][0], ra[0][1], ra[0][2], ra[0][3], ra[1][0], ra[1][1], ra[1][2], ra[1][3]};
-    bf16x8 sa[3];
-    split3_bf16(av, sa[0], sa[1], sa[2]);
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl)
-      *reinterpret_cast<bf16x8*>(&Aimg[buf][pl][a_row * 32 + (a_k >> 3) * 16]) = sa[pl];
-    const float bv[8] = {rb[0][0], rb[0][1], rb[0][2], rb[0][3], rb[1][0], rb[1][1], rb[1][2], rb[1][3]};
-    bf16x8 sb[3];
-    split3_bf16(bv, sb[0], sb[1], sb[2]);
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl)
-      *reinterpret_cast<bf16x8*>(&Bimg[buf][pl][swz_off(b_k, b_n >> 3)]) = sb[pl];
+    MP_STASH8(Aimg[buf], [a_row * 32 + (a_k >> 3) * 16], ra[0], ra[1]);
+    MP_STASH8(Bimg[buf], [swz_off(b_k, b_n >> 3)], rb[0], rb[1]);
   };
 
-  f32x16 acc[2][TN];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  f32x16 acc[2][2];
+  MP_ZERO_ACC(acc, 2, 2);
 
   fetch(0);
   stash(0);
@@ -154,20 +154,20 @@ __global__ __launch_bounds__(kBlock, TN == 2 ? 3 : 1) void dense_fused_kernel(co
     if (t + 1 < ntiles) fetch((t + 1) * BK);          // in flight while the MFMAs below run
     {
       // the K = 16 tile as one step on the bf16 matrix pipe: operands were split when they were staged
-      bf16x8 as[2][3], bs3[TN][3];
+      bf16x8 as[2][3], bs3[2][3];
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl)
           as[i][pl] = *reinterpret_cast<const bf16x8*>(&Aimg[buf][pl][(wm * 64 + i * 32 + fr) * 32 + fk * 16]);
 #pragma unroll
-      for (int j = 0; j < TN; ++j)
+      for (int j = 0; j < 2; ++j)
 #pragma unroll
-        for (int pl = 0; pl < 3; ++pl) bs3[j][pl] = tr_read8(Bimg[buf][pl], wn * (32 * TN) + j * 32, lane);
+        for (int pl = 0; pl < 3; ++pl) bs3[j][pl] = tr_read8(Bimg[buf][pl], wn * 64 + j * 32, lane);
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) mfma6(acc[i][j], as[i], bs3[j]);
+        for (int j = 0; j < 2; ++j) mfma6(acc[i][j], as[i], bs3[j]);
     }
     if (t + 1 < ntiles) stash(buf ^ 1);               // the other buffer: nobody reads it this iteration
     __syncthreads();
@@ -175,8 +175,8 @@ __global__ __launch_bounds__(kBlock, TN == 2 ? 3 : 1) void dense_fused_kernel(co
 
   // epilogue: C/D layout of the 32x32 f32 tile: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
 #pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    const int col = n0 + wn * (32 * TN) + j * 32 + fr;
+  for (int j = 0; j < 2; ++j) {
+    const int col = n0 + wn * 64 + j * 32 + fr;
     const bool col_ok = col < d;
     const float bv = (bias != nullptr && col_ok) ? bias[col] : 0.f;
 #pragma unroll
@@ -192,6 +192,13 @@ __global__ __launch_bounds__(kBlock, TN == 2 ? 3 : 1) void dense_fused_kernel(co
   }
 }
 
+
+// the node rows [mb, me) of chunk c of the split over nodes (all weight-gradient kernels below)
+struct ChunkRows { int64_t mb, me; };
+__device__ __forceinline__ ChunkRows chunk_rows(int64_t c, int64_t chunk, int64_t M) {
+  const int64_t mb = c * chunk;
+  return {mb, mb + chunk < M ? mb + chunk : M};
+}
 
 // Weight gradient of the transform: dW[F, d] = P^T g = sum_m P[m, :]^T g[m, :]  (the reduction runs over
 // the node axis).  Both MFMA operands are plain row tiles with k = node index — A[i = f][k = m] = P[m][f],
@@ -221,8 +228,8 @@ __global__ __launch_bounds__(kBlock, 3) void dense_wgrad_kernel(const float* __r
   const int tile = blockIdx.x % (tf * td);
   const int64_t c = blockIdx.x / (tf * td);
   const int f0 = (tile / td) * BT, d0 = (tile % td) * BT;
-  const int64_t mb = c * chunk;
-  const int64_t me = mb + chunk < M ? mb + chunk : M;
+  const ChunkRows cr = chunk_rows(c, chunk, M);
+  const int64_t mb = cr.mb, me = cr.me;
 
   const int l_row = tid >> 4;              // 0..15: node row inside the tile
   const int l_col = (tid & 15) * 8;        // 8 consecutive columns
@@ -282,12 +289,7 @@ __global__ __launch_bounds__(kBlock, 3) void dense_wgrad_kernel(const float* __r
     }
   };
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  MP_ZERO_ACC(acc, 2, 2);
 
   // the bias gradient (column sums of g) rides along: the blocks of the first f-tile see every element of their
   // g columns once, in registers, on its way to LDS
@@ -380,8 +382,8 @@ __global__ __launch_bounds__(kBlock, 2) void dense_wgrad_wide_kernel(const float
   const int tile = blockIdx.x % (tf * td);
   const int64_t c = blockIdx.x / (tf * td);
   const int f0 = (tile / td) * BF, d0 = (tile % td) * BD;
-  const int64_t mb = c * chunk;
-  const int64_t me = mb + chunk < M ? mb + chunk : M;
+  const ChunkRows cr = chunk_rows(c, chunk, M);
+  const int64_t mb = cr.mb, me = cr.me;
 
   const int l_row = tid >> 4;              // 0..15: node row inside the tile
   const int l_col = (tid & 15) * 8;        // 8 consecutive columns (of each 128-column half for P)
@@ -420,26 +422,12 @@ __global__ __launch_bounds__(kBlock, 2) void dense_wgrad_wide_kernel(const float
     const int off = swz_off(l_row, l_col >> 3);
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      const float pv[8] = {rp[h][0][0], rp[h][0][1], rp[h][0][2], rp[h][0][3], rp[h][1][0], rp[h][1][1], rp[h][1][2],
-                           rp[h][1][3]};
-      bf16x8 sp[3];
-      split3_bf16(pv, sp[0], sp[1], sp[2]);
-#pragma unroll
-      for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<bf16x8*>(&Pimg[buf][pl][h][off]) = sp[pl];
+      MP_STASH8(Pimg[buf], [h][off], rp[h][0], rp[h][1]);
     }
-    const float gv[8] = {rg[0][0], rg[0][1], rg[0][2], rg[0][3], rg[1][0], rg[1][1], rg[1][2], rg[1][3]};
-    bf16x8 sg[3];
-    split3_bf16(gv, sg[0], sg[1], sg[2]);
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<bf16x8*>(&Gimg[buf][pl][off]) = sg[pl];
+    MP_STASH8(Gimg[buf], [off], rg[0], rg[1]);
   };
   f32x16 acc[2][4];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  MP_ZERO_ACC(acc, 2, 4);
 
   const bool do_bias = bias_slabs != nullptr && f0 == 0;
   float bs[8];
@@ -541,8 +529,8 @@ __global__ __launch_bounds__(WPC_THREADS, 3) void dense_wgrad_pc_kernel(const fl
   const int tile = (int)(blockIdx.x % (unsigned)(tf * td));
   const int64_t c = blockIdx.x / (unsigned)(tf * td);
   const int f0 = (tile / td) * 256, d0 = (tile % td) * 128 * DT;
-  const int64_t mb = c * chunk;
-  const int64_t me = mb + chunk < M ? mb + chunk : M;
+  const ChunkRows cr = chunk_rows(c, chunk, M);
+  const int64_t mb = cr.mb, me = cr.me;
   const int64_t ntiles = (me - mb + BK - 1) / BK;      // >= 1: the host launches ceil(M / chunk) workgroups
 
   // Both roles run `nsteps` steps, a multiple of NSET: the tiles past the end of the range are all zero (rows >= me are
@@ -670,12 +658,7 @@ __global__ __launch_bounds__(WPC_THREADS, 3) void dense_wgrad_pc_kernel(const fl
     const int f_lo = DT == 2 ? wf * 64 : wf * 32;              // first f row of this wave
     const int fr = lane & 31, fk = lane >> 5;
     f32x16 acc[NI][4];
-#pragma unroll
-    for (int i = 0; i < NI; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    MP_ZERO_ACC(acc, NI, 4);
     role_barrier();                                    // stage 0 holds tile 0
     for (int64_t t = 0; t < nsteps; ++t) {
       const int buf = (int)(t & 1);
@@ -728,8 +711,8 @@ __global__ __launch_bounds__(kBlock) void narrow_wgrad_kernel(const float* __res
                                                               float* __restrict__ bias_slabs) {
   const int c = blockIdx.y * kBlock + threadIdx.x;
   const int64_t ch = blockIdx.x;
-  const int64_t mb = ch * chunk;
-  const int64_t me = mb + chunk < M ? mb + chunk : M;
+  const ChunkRows cr = chunk_rows(ch, chunk, M);
+  const int64_t mb = cr.mb, me = cr.me;
   if (c >= d) return;
   float acc[8];
 #pragma unroll
@@ -785,8 +768,8 @@ __global__ __launch_bounds__(kBlock) void narrow_wgrad_vec_kernel(const float* _
   const int nrl = kBlock / ncg;                 // row lanes
   const int cg = threadIdx.x % ncg, rl = threadIdx.x / ncg;
   const int64_t ch = blockIdx.x;
-  const int64_t mb = ch * chunk;
-  const int64_t me = mb + chunk < M ? mb + chunk : M;
+  const ChunkRows cr = chunk_rows(ch, chunk, M);
+  const int64_t mb = cr.mb, me = cr.me;
   f32x4 acc[FT];
 #pragma unroll
   for (int f = 0; f < FT; ++f) acc[f] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -850,8 +833,8 @@ __global__ __launch_bounds__(kBlock) void narrow_out_wgrad_kernel(const float* _
   __shared__ float red[64][4][17];              // [column group][f][d (+ pad)]; bias partials in red[0][0][..] afterwards
   const int ncg = F >> 2;                       // column groups handled per pass (<= 64: F <= 256 per pass)
   const int64_t ch = blockIdx.x;
-  const int64_t mb = ch * chunk;
-  const int64_t me = mb + chunk < M ? mb + chunk : M;
+  const ChunkRows cr = chunk_rows(ch, chunk, M);
+  const int64_t mb = cr.mb, me = cr.me;
   float* slab = slabs + ch * (int64_t)F * d;
   for (int cg0 = 0; cg0 < ncg; cg0 += 64) {     // F > 256: further passes over the rows
     const int ng = ncg - cg0 < 64 ? ncg - cg0 : 64;
@@ -989,19 +972,14 @@ int mp_dense_fused_f32(const float* P, int64_t ldp, const float* W, const float*
   if (M == 0) return MP_OK;
   // 16-byte vector loads need operand widths in multiples of 8 (F) / 4 (d) and aligned rows; else scalar loaders
   const bool vec = !(F % 8 || d % 4 || ldp % 4 || (Q && ldq % 4)) && al16(P) && al16(W) && al16(Q) && al16(Wid);
-  const int tn = 2;   // 128-column block tile (a 256-column tile needs 297 registers, one wave per SIMD: 25 % slower, not built)
-  const int bn = 64 * tn;
-  const int64_t nblocks = ceil_div(d, bn) * ceil_div(M, BM);
+  const int64_t nblocks = ceil_div(d, BN) * ceil_div(M, BM);
   if (nblocks >= INT32_MAX) return MP_ERR_UNSUPPORTED;
   dim3 grid((unsigned)nblocks);
   hipStream_t st = as_stream(stream);
-#define MP_DENSE(DUALV, TNV, VECV)                                                                        \
-  hipLaunchKernelGGL((dense_fused_kernel<DUALV, TNV, VECV>), grid, dim3(kBlock), 0, st, P, ldp, W, Q, ldq, Wid, \
-                     bias, act, out, ldo, M, F, d)
-  if (!vec) { if (Q) MP_DENSE(true, 2, false); else MP_DENSE(false, 2, false); }
-  else if (Q) MP_DENSE(true, 2, true);
-  else MP_DENSE(false, 2, true);
-#undef MP_DENSE
+  with_bools(Q != nullptr, vec, [&](auto dual, auto v) {
+    hipLaunchKernelGGL((dense_fused_kernel<decltype(dual)::value, decltype(v)::value>), grid, dim3(kBlock), 0, st, P, ldp,
+                       W, Q, ldq, Wid, bias, act, out, ldo, M, F, d);
+  });
   MP_LAUNCH_CHECK();
   return MP_OK;
 }
@@ -1009,6 +987,20 @@ int mp_dense_fused_f32(const float* P, int64_t ldp, const float* W, const float*
 int mp_dense_wgrad_ws_bytes(int64_t M, int32_t F, int32_t d, size_t* bytes_host) {
   if (!bytes_host || M < 0 || F <= 0 || d <= 0) return MP_ERR_INVALID_ARG;
   *bytes_host = (size_t)ceil_div(M > 0 ? M : 1, wgrad_chunk(M, F, d)) * ((size_t)F * d + d) * 4;   // + the bias partials
+  return MP_OK;
+}
+
+// the tail of every weight-gradient route: dW and the bias gradient from their n_slab partials, in slab order
+static int reduce_slabs(const void* ws, int64_t n_slab, int32_t F, int32_t d, float* dW, const float* bias_slabs,
+                        float* dbias, hipStream_t st) {
+  hipLaunchKernelGGL(slab_reduce_kernel, dim3(flat_grid((int64_t)F * d * 16)), dim3(kBlock), 0, st, (const float*)ws,
+                     n_slab, (int64_t)F * d, dW);
+  MP_LAUNCH_CHECK();
+  if (dbias) {
+    hipLaunchKernelGGL(slab_reduce_kernel, dim3(flat_grid((int64_t)d * 16)), dim3(kBlock), 0, st, bias_slabs, n_slab,
+                       (int64_t)d, dbias);
+    MP_LAUNCH_CHECK();
+  }
   return MP_OK;
 }
 
@@ -1037,43 +1029,23 @@ static int wgrad_common(const float* P, int64_t ldp, const float* G, int64_t ldg
     const bool nvec = d % 4 == 0 && d <= 4 * kBlock && kBlock % (d / 4) == 0 && ldg % 4 == 0 && al16(G) &&
                       (!Y || (ldy % 4 == 0 && al16(Y))) && (!GM || (ldgm % 4 == 0 && al16(GM))) &&
                       al16(ws) && (!bias_slabs || al16(bias_slabs));
-    if (nvec) {
-#define MP_NARROW(RELUV, FTV)                                                                                       \
-  hipLaunchKernelGGL((narrow_wgrad_vec_kernel<RELUV, FTV>), dim3((unsigned)n_chunk), dim3(kBlock), 0, st, P, ldp, G, \
-                     ldg, Y, ldy, GM, ldgm, M, F, d, chunk, (float*)ws, bias_slabs)
-      if (Y) { if (F == 1) MP_NARROW(true, 1); else MP_NARROW(true, 8); }
-      else { if (F == 1) MP_NARROW(false, 1); else MP_NARROW(false, 8); }
-#undef MP_NARROW
-    } else if (Y)
-      hipLaunchKernelGGL(narrow_wgrad_kernel<true>, ngrid, dim3(kBlock), 0, st, P, ldp, G, ldg, Y, ldy, GM, ldgm, M, F,
-                         d, chunk, (float*)ws, bias_slabs);
-    else
-      hipLaunchKernelGGL(narrow_wgrad_kernel<false>, ngrid, dim3(kBlock), 0, st, P, ldp, G, ldg, Y, ldy, GM, ldgm, M,
-                         F, d, chunk, (float*)ws, bias_slabs);
+    with_bools(Y != nullptr, F == 1, [&](auto relu, auto one) {
+      constexpr bool R = decltype(relu)::value;
+      if (nvec)
+        hipLaunchKernelGGL((narrow_wgrad_vec_kernel<R, decltype(one)::value ? 1 : 8>), dim3((unsigned)n_chunk),
+                           dim3(kBlock), 0, st, P, ldp, G, ldg, Y, ldy, GM, ldgm, M, F, d, chunk, (float*)ws, bias_slabs);
+      else
+        hipLaunchKernelGGL(narrow_wgrad_kernel<R>, ngrid, dim3(kBlock), 0, st, P, ldp, G, ldg, Y, ldy, GM, ldgm, M, F,
+                           d, chunk, (float*)ws, bias_slabs);
+    });
     MP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(flat_grid((int64_t)F * d * 16)), dim3(kBlock), 0, st, (const float*)ws,
-                       n_chunk, (int64_t)F * d, dW);
-    MP_LAUNCH_CHECK();
-    if (dbias) {
-      hipLaunchKernelGGL(slab_reduce_kernel, dim3(flat_grid((int64_t)d * 16)), dim3(kBlock), 0, st,
-                         (const float*)bias_slabs, n_chunk, (int64_t)d, dbias);
-      MP_LAUNCH_CHECK();
-    }
-    return MP_OK;
+    return reduce_slabs(ws, n_chunk, F, d, dW, bias_slabs, dbias, st);
   }
   if (!Y && d <= 16 && F % 4 == 0 && ldp % 4 == 0 && al16(P)) {   // the classifier head's shape
     hipLaunchKernelGGL(narrow_out_wgrad_kernel, dim3((unsigned)n_chunk), dim3(kBlock), 0, st, P, ldp, G, ldg, M, F, d,
                        chunk, (float*)ws, bias_slabs);
     MP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(flat_grid((int64_t)F * d * 16)), dim3(kBlock), 0, st, (const float*)ws,
-                       n_chunk, (int64_t)F * d, dW);
-    MP_LAUNCH_CHECK();
-    if (dbias) {
-      hipLaunchKernelGGL(slab_reduce_kernel, dim3(flat_grid((int64_t)d * 16)), dim3(kBlock), 0, st,
-                         (const float*)bias_slabs, n_chunk, (int64_t)d, dbias);
-      MP_LAUNCH_CHECK();
-    }
-    return MP_OK;
+    return reduce_slabs(ws, n_chunk, F, d, dW, bias_slabs, dbias, st);
   }
   if (vec && F > 128 && d >= 64 && F % 8 == 0 && d % 8 == 0) {   // loaders + MFMA waves, the whole gradient per workgroup
     const int64_t pc_chunk = wgrad_pc_chunk(M);
@@ -1081,61 +1053,29 @@ static int wgrad_common(const float* P, int64_t ldp, const float* G, int64_t ldg
     float* pc_bias = dbias ? (float*)ws + (size_t)n_pc * F * d : nullptr;
     const int64_t pc_tiles = ceil_div(F, 256) * ceil_div(d, d > 128 ? 256 : 128);
     if (n_pc * pc_tiles >= INT32_MAX) return MP_ERR_UNSUPPORTED;
-#define MP_WPC(RELUV, DTV)                                                                                          \
-  hipLaunchKernelGGL((dense_wgrad_pc_kernel<RELUV, DTV>), dim3((unsigned)(n_pc * pc_tiles)), dim3(WPC_THREADS), 0, st, P, ldp, G, \
-                     ldg, Y, ldy, GM, ldgm, M, F, d, pc_chunk, (float*)ws, pc_bias)
-    if (d > 128) { if (Y) MP_WPC(true, 2); else MP_WPC(false, 2); }
-    else { if (Y) MP_WPC(true, 1); else MP_WPC(false, 1); }
-#undef MP_WPC
+    with_bools(Y != nullptr, d > 128, [&](auto relu, auto two) {
+      hipLaunchKernelGGL((dense_wgrad_pc_kernel<decltype(relu)::value, decltype(two)::value ? 2 : 1>),
+                         dim3((unsigned)(n_pc * pc_tiles)), dim3(WPC_THREADS), 0, st, P, ldp, G, ldg, Y, ldy, GM, ldgm, M,
+                         F, d, pc_chunk, (float*)ws, pc_bias);
+    });
     MP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(flat_grid((int64_t)F * d * 16)), dim3(kBlock), 0, st, (const float*)ws,
-                       n_pc, (int64_t)F * d, dW);
-    MP_LAUNCH_CHECK();
-    if (dbias) {
-      hipLaunchKernelGGL(slab_reduce_kernel, dim3(flat_grid((int64_t)d * 16)), dim3(kBlock), 0, st,
-                         (const float*)pc_bias, n_pc, (int64_t)d, dbias);
-      MP_LAUNCH_CHECK();
-    }
-    return MP_OK;
+    return reduce_slabs(ws, n_pc, F, d, dW, pc_bias, dbias, st);
   }
-  if (vec && F > 128) {   // the 256 x 128 tile
-    const int64_t wtiles = ceil_div(F, 256) * ceil_div(d, 128);
-    if (wtiles * n_chunk >= INT32_MAX) return MP_ERR_UNSUPPORTED;
-    const dim3 wgrid((unsigned)(wtiles * n_chunk));
-    if (Y)
-      hipLaunchKernelGGL(dense_wgrad_wide_kernel<true>, wgrid, dim3(kBlock), 0, st, P, ldp, G, ldg, Y, ldy, GM, ldgm, M,
-                         F, d, chunk, (float*)ws, bias_slabs);
+  const bool wide = vec && F > 128;   // the 256 x 128 tile; else the 128 x 128 tile
+  const int64_t wtiles = wide ? ceil_div(F, 256) * ceil_div(d, 128) : tiles;
+  if (wtiles * n_chunk >= INT32_MAX) return MP_ERR_UNSUPPORTED;
+  const dim3 grid((unsigned)(wtiles * n_chunk));
+  with_bools(Y != nullptr, vec, [&](auto relu, auto v) {
+    constexpr bool R = decltype(relu)::value;
+    if (wide)
+      hipLaunchKernelGGL(dense_wgrad_wide_kernel<R>, grid, dim3(kBlock), 0, st, P, ldp, G, ldg, Y, ldy, GM, ldgm, M, F, d,
+                         chunk, (float*)ws, bias_slabs);
     else
-      hipLaunchKernelGGL(dense_wgrad_wide_kernel<false>, wgrid, dim3(kBlock), 0, st, P, ldp, G, ldg, Y, ldy, GM, ldgm, M,
-                         F, d, chunk, (float*)ws, bias_slabs);
-    MP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(flat_grid((int64_t)F * d * 16)), dim3(kBlock), 0, st, (const float*)ws,
-                       n_chunk, (int64_t)F * d, dW);
-    MP_LAUNCH_CHECK();
-    if (dbias) {
-      hipLaunchKernelGGL(slab_reduce_kernel, dim3(flat_grid((int64_t)d * 16)), dim3(kBlock), 0, st,
-                         (const float*)bias_slabs, n_chunk, (int64_t)d, dbias);
-      MP_LAUNCH_CHECK();
-    }
-    return MP_OK;
-  }
-  const dim3 grid((unsigned)(tiles * n_chunk));
-#define MP_WGRAD(VECV, RELUV)                                                                                     \
-  hipLaunchKernelGGL((dense_wgrad_kernel<VECV, RELUV>), grid, dim3(kBlock), 0, st, P, ldp, G, ldg, Y, ldy, GM,     \
-                     ldgm, M, F, d, chunk, (float*)ws, bias_slabs)
-  if (Y) { if (vec) MP_WGRAD(true, true); else MP_WGRAD(false, true); }
-  else { if (vec) MP_WGRAD(true, false); else MP_WGRAD(false, false); }
-#undef MP_WGRAD
+      hipLaunchKernelGGL((dense_wgrad_kernel<decltype(v)::value, R>), grid, dim3(kBlock), 0, st, P, ldp, G, ldg, Y, ldy,
+                         GM, ldgm, M, F, d, chunk, (float*)ws, bias_slabs);
+  });
   MP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(slab_reduce_kernel, dim3(flat_grid((int64_t)F * d * 16)), dim3(kBlock), 0, st, (const float*)ws,
-                     n_chunk, (int64_t)F * d, dW);
-  MP_LAUNCH_CHECK();
-  if (dbias) {
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(flat_grid((int64_t)d * 16)), dim3(kBlock), 0, st,
-                       (const float*)bias_slabs, n_chunk, (int64_t)d, dbias);
-    MP_LAUNCH_CHECK();
-  }
-  return MP_OK;
+  return reduce_slabs(ws, n_chunk, F, d, dW, bias_slabs, dbias, st);
 }
 
 int mp_dense_wgrad_f32(const float* P, int64_t ldp, const float* G, int64_t ldg, int64_t M, int32_t F,

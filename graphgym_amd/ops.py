@@ -277,30 +277,10 @@ def _raw_agg_dense(g, x, W, bias=None, relu=False, S=None, self_scale=0.0, want_
     return out, P
 
 
-def _raw_dense_wgrad(P, G, want_bias=False):
-    """P^T @ G on the engine's split-K MFMA kernel (None when the shape is outside it); with want_bias the pair
-    (P^T @ G, column sums of G) — the bias gradient comes out of the same pass over G"""
-    L = lib()
-    M, F = P.shape
-    d = G.size(1)
-    out = torch.empty((F, d), dtype=torch.float32, device=P.device)
-    db = torch.empty(d, dtype=torch.float32, device=P.device) if want_bias else None
-    with torch.cuda.device(P.device):
-        nb = C.c_size_t(0)
-        check(L.mp_dense_wgrad_ws_bytes(M, F, d, C.byref(nb)))
-        ws = torch.empty(max(nb.value, 1), dtype=torch.uint8, device=P.device)
-        st = L.mp_dense_wgrad_f32(ptr(P), P.stride(0), ptr(G), G.stride(0), M, F, d, ptr(out), ptr(db), ptr(ws),
-                                  nb.value, _stream())
-    if st in (2, 5):
-        return (None, None) if want_bias else None
-    check(st, "mp_dense_wgrad_f32")
-    return (out, db) if want_bias else out
-
-
-def _raw_dense_wgrad_relu(P, G, Y, want_bias=False, want_gm=True, gm_out=None):
-    """(P^T (G * [Y > 0]), its column sums or None, G * [Y > 0]) in one pass (mp_dense_wgrad_relu_f32): the weight-gradient
-    kernel masks the incoming gradient by the forward's ReLU pattern as it reads it and writes the masked gradient out
-    for the input-gradient launch; None when the shape is outside the kernel"""
+def _launch_dense_wgrad(P, G, Y=None, want_bias=False, want_gm=False, gm_out=None):
+    """one weight-gradient pass, mp_dense_wgrad_f32 or (Y given) mp_dense_wgrad_relu_f32: sizes and allocates the workspace
+    and the outputs; (P^T g, column sums of g or None, g or None) with g = G or G * [Y > 0]; None when the shape is
+    outside the kernel"""
     L = lib()
     M, F = P.shape
     d = G.size(1)
@@ -314,13 +294,31 @@ def _raw_dense_wgrad_relu(P, G, Y, want_bias=False, want_gm=True, gm_out=None):
         nb = C.c_size_t(0)
         check(L.mp_dense_wgrad_ws_bytes(M, F, d, C.byref(nb)))
         ws = torch.empty(max(nb.value, 1), dtype=torch.uint8, device=P.device)
-        st = L.mp_dense_wgrad_relu_f32(ptr(P), P.stride(0), ptr(G), G.stride(0), ptr(Y), Y.stride(0), ptr(gm),
-                                       gm.stride(0) if gm is not None else 0, M, F, d, ptr(out), ptr(db), ptr(ws),
-                                       nb.value, _stream())
+        tail = (M, F, d, ptr(out), ptr(db), ptr(ws), nb.value, _stream())
+        if Y is None:
+            name, st = "mp_dense_wgrad_f32", L.mp_dense_wgrad_f32(ptr(P), P.stride(0), ptr(G), G.stride(0), *tail)
+        else:
+            name, st = "mp_dense_wgrad_relu_f32", L.mp_dense_wgrad_relu_f32(
+                ptr(P), P.stride(0), ptr(G), G.stride(0), ptr(Y), Y.stride(0), ptr(gm),
+                gm.stride(0) if gm is not None else 0, *tail)
     if st in (2, 5):
         return None
-    check(st, "mp_dense_wgrad_relu_f32")
+    check(st, name)
     return out, db, gm
+
+
+def _raw_dense_wgrad(P, G, want_bias=False):
+    """P^T @ G on the engine's split-K MFMA kernel (None when the shape is outside it); with want_bias the pair
+    (P^T @ G, column sums of G) — the bias gradient comes out of the same pass over G"""
+    r = _launch_dense_wgrad(P, G, want_bias=want_bias) or (None, None)
+    return r[:2] if want_bias else r[0]
+
+
+def _raw_dense_wgrad_relu(P, G, Y, want_bias=False, want_gm=True, gm_out=None):
+    """(P^T (G * [Y > 0]), its column sums or None, G * [Y > 0]) in one pass (mp_dense_wgrad_relu_f32): the weight-gradient
+    kernel masks the incoming gradient by the forward's ReLU pattern as it reads it and writes the masked gradient out
+    for the input-gradient launch; None when the shape is outside the kernel"""
+    return _launch_dense_wgrad(P, G, Y, want_bias, want_gm, gm_out)
 
 
 def _wgrad_and_bias(X, g, need_w, need_b):
@@ -338,6 +336,28 @@ def _wgrad_and_bias(X, g, need_w, need_b):
         if dW is None:
             dW = X.t() @ g
     return dW, (g.sum(0) if need_b else None)
+
+
+def _concat_wgrad(a, b, g, out, ku, relu, need_wa, need_wb, has_bias, need_gm):
+    """the weight side of the backward of out = act([a Wa ‖ b Wb] + bias): (g masked by the ReLU — None if nobody reads
+    it —, dWa, dWb, dba, dbb).  b None: its rows were not kept (no dWb)"""
+    if relu and need_wa and need_wb and b is not None:
+        # the ReLU mask rides in the two weight-gradient passes (one per half of the output), which also leave the masked
+        # halves in one buffer for the input-gradient launches (no threshold_backward pass); the buffer is written only
+        # when an input gradient will read it (a first layer has none)
+        mg = placement.empty_or_torch(tuple(g.shape), g.device, reads=(g, out), streaming=True) if need_gm else None
+        rs = _raw_dense_wgrad_relu(a, g[:, :ku], out[:, :ku], want_bias=has_bias, want_gm=need_gm,
+                                   gm_out=None if mg is None else mg[:, :ku])
+        rn = None if rs is None else _raw_dense_wgrad_relu(b, g[:, ku:], out[:, ku:], want_bias=has_bias,
+                                                           want_gm=need_gm,
+                                                           gm_out=None if mg is None else mg[:, ku:])
+        if rs is not None and rn is not None:
+            return mg, rs[0], rn[0], rs[1], rn[1]
+    if relu:
+        g = torch.ops.aten.threshold_backward(g, out, 0.0)
+    dWa, dba = _wgrad_and_bias(a, g[:, :ku], need_wa, has_bias)
+    dWb, dbb = _wgrad_and_bias(b, g[:, ku:], need_wb, has_bias)
+    return g, dWa, dWb, dba, dbb
 
 
 def _dense_into(out_view, P, W, bias, relu):
@@ -375,26 +395,9 @@ class _ConcatDense(torch.autograd.Function):
     def backward(ctx, g):
         x, m, Ws, Wn, out = ctx.saved_tensors
         ku = ctx.ku
-        g = g.contiguous()
-        need_in = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
-        done = False
-        if ctx.relu and ctx.needs_input_grad[2] and ctx.needs_input_grad[3]:
-            # the ReLU mask rides in the two weight-gradient passes (one per half of the output); the masked halves are
-            # written only when an input gradient will read them (a first layer has none)
-            mg = placement.empty_or_torch(tuple(g.shape), g.device, reads=(g, out), streaming=True) if need_in else None
-            rs = _raw_dense_wgrad_relu(x, g[:, :ku], out[:, :ku], want_bias=ctx.has_bias, want_gm=need_in,
-                                       gm_out=None if mg is None else mg[:, :ku])
-            rn = None if rs is None else _raw_dense_wgrad_relu(m, g[:, ku:], out[:, ku:], want_bias=ctx.has_bias,
-                                                               want_gm=need_in,
-                                                               gm_out=None if mg is None else mg[:, ku:])
-            if rs is not None and rn is not None:
-                (dWs, dbs, _), (dWn, dbn, _) = rs, rn
-                g, done = mg, True
-        if not done:
-            if ctx.relu:
-                g = torch.ops.aten.threshold_backward(g, out, 0.0)
-            dWs, dbs = _wgrad_and_bias(x, g[:, :ku], ctx.needs_input_grad[2], ctx.has_bias)
-            dWn, dbn = _wgrad_and_bias(m, g[:, ku:], ctx.needs_input_grad[3], ctx.has_bias)
+        g, dWs, dWn, dbs, dbn = _concat_wgrad(x, m, g.contiguous(), out, ku, ctx.relu, ctx.needs_input_grad[2],
+                                              ctx.needs_input_grad[3], ctx.has_bias,
+                                              ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
         dx = times_wt(g[:, :ku], Ws) if ctx.needs_input_grad[0] else None     # strided views: the kernels take leading dimensions
         dm = times_wt(g[:, ku:], Wn) if ctx.needs_input_grad[1] else None
         db = torch.cat([dbs, dbn]) if ctx.has_bias else None
@@ -432,26 +435,8 @@ class _SageConcatFused(torch.autograd.Function):
     def backward(ctx, gout):
         x, P, Ws, Wn, out = ctx.saved_tensors
         ku = ctx.ku
-        gm = gout.contiguous()
-        done = False
-        if ctx.relu and ctx.needs_input_grad[1] and ctx.needs_input_grad[2] and P is not None:
-            # the ReLU mask rides in the two weight-gradient passes (one per half of the concatenated output), which
-            # also leave the masked halves in one buffer for the input-gradient launches: no threshold_backward pass
-            need_gm = ctx.needs_input_grad[0]
-            mg = placement.empty_or_torch(tuple(gm.shape), gm.device, reads=(gm, out), streaming=True) if need_gm else None
-            rs = _raw_dense_wgrad_relu(x, gm[:, :ku], out[:, :ku], want_bias=ctx.has_bias, want_gm=need_gm,
-                                       gm_out=None if mg is None else mg[:, :ku])
-            rn = None if rs is None else _raw_dense_wgrad_relu(P, gm[:, ku:], out[:, ku:], want_bias=ctx.has_bias,
-                                                               want_gm=need_gm,
-                                                               gm_out=None if mg is None else mg[:, ku:])
-            if rs is not None and rn is not None:
-                (dWs, dbs, _), (dWn, dbn, _) = rs, rn
-                gm, done = mg, True
-        if not done:
-            if ctx.relu:
-                gm = torch.ops.aten.threshold_backward(gm, out, 0.0)
-            dWs, dbs = _wgrad_and_bias(x, gm[:, :ku], ctx.needs_input_grad[1], ctx.has_bias)
-            dWn, dbn = _wgrad_and_bias(P, gm[:, ku:], ctx.needs_input_grad[2], ctx.has_bias)
+        gm, dWs, dWn, dbs, dbn = _concat_wgrad(x, P, gout.contiguous(), out, ku, ctx.relu, ctx.needs_input_grad[1],
+                                               ctx.needs_input_grad[2], ctx.has_bias, ctx.needs_input_grad[0])
         gs, gn = (gm[:, :ku], gm[:, ku:]) if gm is not None else (None, None)
         db = torch.cat([dbs, dbn]) if ctx.has_bias else None
         dx = None

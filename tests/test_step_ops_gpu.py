@@ -49,6 +49,91 @@ def test_wgrad_with_relu_mask(dev, M, Fi, d):
     assert gm4.numel() == 0 and torch.equal(dW4, dW)
 
 
+# Every weight-gradient kernel of gemm.hip, by the conditions of wgrad_common in their order (operands here are
+# contiguous and 16-byte aligned, so vec = F % 4 == 0 and d % 4 == 0; chunk = 4096 rows unless noted):
+WGRAD_ROUTES = [
+    # F > 8, d > 16, F <= 128, vec: dense_wgrad_kernel<true, Y>, one 128 x 128 tile, two chunks
+    (5000, 128, 64),
+    # the same kernel with both tile edges ragged (F = 100, d = 36 < 128) and one chunk
+    (300, 100, 36),
+    # F % 4 != 0: not vec, so neither loader/MFMA waves nor the 256-row tile: dense_wgrad_kernel<false, Y>, 2 x 2 tiles
+    (300, 131, 130),
+    # vec, F > 128, F % 8 == 4 (no loader/MFMA waves): dense_wgrad_wide_kernel<Y>, 2 f x 2 d tiles, ragged, two chunks
+    (5000, 260, 132),
+    # vec, F > 128, d < 64 (no loader/MFMA waves): dense_wgrad_wide_kernel<Y>, one tile with a quarter of its columns
+    (300, 256, 32),
+    # vec, F > 128, d >= 64, F % 8 == d % 8 == 0, d <= 128: dense_wgrad_pc_kernel<Y, 1>; ranges of 4096 rows and 1 row
+    (4097, 136, 72),
+    # the same conditions, d > 128: dense_wgrad_pc_kernel<Y, 2>, one 256 x 256 tile with ragged f; ranges of 4096 and 1
+    (4097, 200, 256),
+    # dense_wgrad_pc_kernel<Y, 2>, 3 f x 2 d tiles; ranges of 4096 and 104 rows, the second ending inside a 16-row tile
+    (4200, 520, 264),
+    # F <= 8 (chunk 2048), d % 4 != 0: not nvec: narrow_wgrad_kernel<Y>
+    (333, 1, 7),
+    # F <= 8, d % 4 == 0 but 256 % (d / 4) != 0: not nvec: narrow_wgrad_kernel<Y>, two column blocks, three chunks
+    (4100, 8, 260),
+    # F == 1, d % 4 == 0, 256 % (d / 4) == 0: narrow_wgrad_vec_kernel<Y, 1>, three chunks
+    (4100, 1, 64),
+    # 1 < F <= 8, nvec: narrow_wgrad_vec_kernel<Y, 8> carrying 5 of its 8 rows
+    (4100, 5, 32),
+]
+# F > 8, no Y, d <= 16, F % 4 == 0: narrow_out_wgrad_kernel (chunk 4096); F = 520 > 256: a second pass over the rows.
+# (With Y these shapes take dense_wgrad_kernel<false, true>, which (300, 131, 130) reaches: without Y only.)
+WGRAD_ROUTES_NO_Y = [(4100, 256, 7), (4100, 520, 10)]
+_WGRAD_CASES = {}
+
+
+def _wgrad_case(M, Fi, d):
+    """the inputs of one shape and its float64 / float32 references, made once and left unchanged"""
+    if (M, Fi, d) not in _WGRAD_CASES:
+        g = torch.Generator().manual_seed(M + d)
+        P = torch.randn(M, Fi, generator=g)
+        G = torch.randn(M, d, generator=g)
+        Y = torch.relu(torch.randn(M, d, generator=g))
+        gm = torch.where(Y > 0, G, torch.zeros_like(G))
+        refs = {y: (P.double().t() @ x.double(), P.t() @ x, x.double().sum(0), x.sum(0)) for y, x in ((False, G), (True, gm))}
+        _WGRAD_CASES[(M, Fi, d)] = (P, G, Y, gm, refs)
+    return _WGRAD_CASES[(M, Fi, d)]
+
+
+@pytest.mark.parametrize("bias", [False, True], ids=["nobias", "bias"])
+@pytest.mark.parametrize("M,Fi,d,mode", [s + (m,) for s in WGRAD_ROUTES
+                                         for m in ("plain", "relu_gm", "relu_no_gm", "relu_in_place")] +
+                         [s + ("plain",) for s in WGRAD_ROUTES_NO_Y])
+def test_wgrad_every_kernel(dev, M, Fi, d, mode, bias):
+    """every instantiation of the weight-gradient kernels, with and without the ReLU mask, the masked gradient written,
+    not written and written over G, with and without the bias gradient: dW and db against float64, the masked gradient
+    exact, and a second call bit for bit (fixed summation order)"""
+    from graphgym_amd import ops
+    relu = mode != "plain"
+    P, G, Y, ref_gm, refs = _wgrad_case(M, Fi, d)
+    dW64, dW32, db64, db32 = refs[relu]
+    Pd, Yd = P.to(dev), Y.to(dev)
+
+    def call():
+        Gd = G.to(dev)                            # afresh: the in-place form overwrites it
+        if not relu:
+            r = ops._raw_dense_wgrad(Pd, Gd, want_bias=bias)
+            return (r[0], r[1], None) if bias else (r, None, None)
+        r = ops._raw_dense_wgrad_relu(Pd, Gd, Yd, want_bias=bias, want_gm=mode == "relu_gm",
+                                      gm_out=Gd if mode == "relu_in_place" else None)
+        assert r is not None
+        return r
+    dW, db, gm = call()
+    assert dW is not None
+    assert_close_all(dW, dW64, 1e-5, ref32=dW32, what="dW")
+    assert (db is not None) == bias
+    if bias:
+        assert_close_all(db, db64, 1e-5, ref32=db32, what="db")
+    if mode in ("relu_gm", "relu_in_place"):
+        assert torch.equal(gm.cpu(), ref_gm)      # the masked gradient is exact
+    else:
+        assert gm is None
+    dW2, db2, gm2 = call()
+    assert torch.equal(dW2, dW) and (not bias or torch.equal(db2, db))
+    assert gm is None or torch.equal(gm2, gm)
+
+
 def test_relu_layers_backward_has_no_separate_mask_pass(dev):
     """the backward of a transform with a ReLU epilogue dispatches mp::dense_wgrad_relu_raw and no aten threshold op"""
     from graphgym_amd import ops
