@@ -92,6 +92,7 @@ PROTOTYPES = {
     "mp_sddmm_dot_stream_f32": (C.c_int, [_p, _p, _i64, _p, _i64, _p, _i64, _i32, _i32, _f32, _p, _p]),
     "mp_sddmm_add_f32": (C.c_int, [_p, _p, _i64, _i64, _p, _p, _f32, _p, _p]),
     "mp_gat_alpha_f32": (C.c_int, [_p, _p, _i64, _i64, _i32, _p, _p, _f32, _p, _p]),
+    "mp_edge_att_alpha_f32": (C.c_int, [_p, _p, _p, _i64, _i64, _i32, _p, _p, _p, _f32, _p, _p]),
     "mp_csr_row_softmax_f32": (C.c_int, [_p, _i64, _i32, _p, _p, _p]),
     "mp_csr_row_softmax_bwd_f32": (C.c_int, [_p, _i64, _i32, _p, _p, _p, _p]),
     "mp_sddmm_grad_f32": (C.c_int, [_p, _p, _i64, _i64, _p, _i64, _p, _i64, _i32, _i32, _p, _p]),
@@ -101,6 +102,9 @@ PROTOTYPES = {
     "mp_spmm_csr_edge_f32": (C.c_int, [_p, _p, _p, _p, _i64, _p, _pi32, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _i32, C.c_int,
                                        _p, _p, _p, _sz, _p]),
     "mp_spmm_edge_bwd_f32": (C.c_int, [_p, _p, _p, _p, _i64, _i64, C.c_int, _p, _i64, _i32, _p, _i64, _p]),
+    "mp_spmm_csr_edge_heads_f32": (C.c_int, [_p, _p, _p, _p, _i64, _p, _pi32, _i32, _p, _i64, _p, _i64, _p, _i64, _p, _i64,
+                                             _i32, C.c_int, _p, _p, _p, _sz, _p]),
+    "mp_spmm_edge_heads_bwd_f32": (C.c_int, [_p, _p, _p, _i32, _p, _i64, _i64, C.c_int, _p, _i64, _i32, _p, _i64, _p]),
     "mp_spmm_heads_max_bwd_f32": (C.c_int, [_p, _p, _i32, _p, _i64, _i32, _p, _i64, _p, _i64, _p]),
     "mp_spmm_heads_max_da_f32": (C.c_int, [_p, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _i32, _i32, _p, _p]),
     "mp_ego_expand": (C.c_int, [_p, _p, _i64, _p, _i64, _i32, _i32, _p, _p, _p, _p, _p]),

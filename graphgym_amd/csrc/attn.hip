@@ -319,23 +319,57 @@ __global__ __launch_bounds__(kBlock) void row_softmax_kernel(const int32_t* __re
 // leaky_relu(a_dst[r, h] + a_src[col[e], h])  (idconv.py:319-327; torch_geometric GATConv [3P]).  The scores are never
 // stored: short rows compute them once into registers; the sweeps of the longer rows recompute them from the two
 // per-node terms, which sit in L2.  Replaces one sddmm_add launch per head + a concatenation + the row softmax of round 1.
-__global__ __launch_bounds__(kBlock) void gat_alpha_kernel(const int32_t* __restrict__ rowptr,
-                                                           const int32_t* __restrict__ col, int64_t N, int32_t heads,
-                                                           const float* __restrict__ a_dst,
-                                                           const float* __restrict__ a_src, float slope, float* out) {
+// EDGE (mp_edge_att_alpha_f32; attconv.py:342-357): the score has a third term a_edge[eid[e], h], one more scalar gather
+// through the entry's input position, loaded next to col (eid < 0: no such term), and a_dst may be absent.
+template <bool EDGE>
+struct AlphaScore {
+  const int32_t* __restrict__ col;
+  const int32_t* __restrict__ eid;
+  const float* __restrict__ a_dst;
+  const float* __restrict__ a_src;
+  const float* __restrict__ a_edge;
+  int32_t heads;
+  float slope;
+
+  __device__ __forceinline__ float dst(int64_t r, int h) const {
+    if constexpr (EDGE) return a_dst ? a_dst[r * heads + h] : 0.f;
+    else return a_dst[r * heads + h];
+  }
+  // the pre-activation of an entry with source c and input position ei, then the leaky ReLU
+  __device__ __forceinline__ float of(float ad, int c, int ei, int h) const {
+    float v = ad + a_src[(int64_t)c * heads + h];
+    if constexpr (EDGE) v += ei >= 0 ? a_edge[(int64_t)ei * heads + h] : 0.f;
+    return v > 0.f ? v : slope * v;
+  }
+  __device__ __forceinline__ float at(float ad, int e, int h) const {
+    if constexpr (EDGE) return of(ad, col[e], eid[e], h);
+    else return of(ad, col[e], -1, h);
+  }
+};
+
+template <bool EDGE>
+__global__ __launch_bounds__(kBlock) void gat_alpha_kernel(const int32_t* __restrict__ rowptr, int64_t N,
+                                                           AlphaScore<EDGE> sc, float* out) {
+  const int heads = sc.heads;
   softmax_row_loop(rowptr, N, kSmShort,
     [&](int64_t r, int e0, int len) {
       int c[kSmShort];
+      int ei[EDGE ? kSmShort : 1];
 #pragma unroll
-      for (int j = 0; j < kSmShort; ++j) c[j] = j < len ? col[e0 + j] : 0;
+      for (int j = 0; j < kSmShort; ++j) {
+        c[j] = j < len ? sc.col[e0 + j] : 0;
+        if constexpr (EDGE) ei[j] = j < len ? sc.eid[e0 + j] : -1;
+      }
       for (int h = 0; h < heads; ++h) {
-        const float ad = a_dst[r * heads + h];
+        const float ad = sc.dst(r, h);
         float v[kSmShort];
         float m = -INFINITY;
 #pragma unroll
         for (int j = 0; j < kSmShort; ++j) {
-          const float t = ad + a_src[(int64_t)c[j] * heads + h];
-          v[j] = j < len ? (t > 0.f ? t : slope * t) : -INFINITY;
+          int eij = -1;
+          if constexpr (EDGE) eij = ei[j];
+          const float t = sc.of(ad, c[j], eij, h);
+          v[j] = j < len ? t : -INFINITY;
           m = fmaxf(m, v[j]);
         }
         float z = 0.f;
@@ -351,46 +385,39 @@ __global__ __launch_bounds__(kBlock) void gat_alpha_kernel(const int32_t* __rest
     },
     [&](int64_t r, int e0, int e1, int trips, int sub) {
       for (int h = 0; h < heads; ++h) {
-        const float ad = a_dst[r * heads + h];
-        auto score = [&](int e) {
-          const float v = ad + a_src[(int64_t)col[e] * heads + h];
-          return v > 0.f ? v : slope * v;
-        };
+        const float ad = sc.dst(r, h);
         float m = -INFINITY;
         for (int t = 0; t < trips; ++t) {
           const int e = e0 + t * kSmLanes + sub;
-          if (e < e1) m = fmaxf(m, score(e));
+          if (e < e1) m = fmaxf(m, sc.at(ad, e, h));
         }
         for (int off = kSmLanes >> 1; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, kWave));
         float z = 0.f;
         for (int t = 0; t < trips; ++t) {
           const int e = e0 + t * kSmLanes + sub;
-          if (e < e1) z += expf(score(e) - m);
+          if (e < e1) z += expf(sc.at(ad, e, h) - m);
         }
         z = wave_sum_seg(z, kSmLanes);
         for (int t = 0; t < trips; ++t) {
           const int e = e0 + t * kSmLanes + sub;
-          if (e < e1) out[(int64_t)e * heads + h] = expf(score(e) - m) / z;
+          if (e < e1) out[(int64_t)e * heads + h] = expf(sc.at(ad, e, h) - m) / z;
         }
       }
     },
     [&](int64_t r, int e0, int e1, float* buf) {
       for (int h = 0; h < heads; ++h) {
-        const float ad = a_dst[r * heads + h];
-        auto score = [&](int e) {
-          const float v = ad + a_src[(int64_t)col[e] * heads + h];
-          return v > 0.f ? v : slope * v;
-        };
+        const float ad = sc.dst(r, h);
         float m = -INFINITY;
 #pragma unroll 4
-        for (int e = e0 + (int)threadIdx.x; e < e1; e += kBlock) m = fmaxf(m, score(e));
+        for (int e = e0 + (int)threadIdx.x; e < e1; e += kBlock) m = fmaxf(m, sc.at(ad, e, h));
         m = block_max_f32(m, buf);
         float z = 0.f;
 #pragma unroll 4
-        for (int e = e0 + (int)threadIdx.x; e < e1; e += kBlock) z += expf(score(e) - m);
+        for (int e = e0 + (int)threadIdx.x; e < e1; e += kBlock) z += expf(sc.at(ad, e, h) - m);
         z = block_sum_f32(z, buf);
 #pragma unroll 4
-        for (int e = e0 + (int)threadIdx.x; e < e1; e += kBlock) out[(int64_t)e * heads + h] = expf(score(e) - m) / z;
+        for (int e = e0 + (int)threadIdx.x; e < e1; e += kBlock)
+          out[(int64_t)e * heads + h] = expf(sc.at(ad, e, h) - m) / z;
       }
     });
 }
@@ -584,8 +611,23 @@ int mp_gat_alpha_f32(const int32_t* rowptr, const int32_t* col, int64_t N, int64
   if (!rowptr || N < 0 || nnz < 0 || heads < 1 || (nnz > 0 && (!col || !a_dst || !a_src || !alpha)))
     return MP_ERR_INVALID_ARG;
   if (N == 0 || nnz == 0) return MP_OK;
-  hipLaunchKernelGGL(gat_alpha_kernel, dim3(flat_grid(N)), dim3(kBlock), 0, as_stream(stream), rowptr, col,
-                     N, heads, a_dst, a_src, slope, alpha);
+  const AlphaScore<false> sc = {col, nullptr, a_dst, a_src, nullptr, heads, slope};
+  hipLaunchKernelGGL(gat_alpha_kernel<false>, dim3(flat_grid(N)), dim3(kBlock), 0, as_stream(stream), rowptr, N, sc,
+                     alpha);
+  MP_LAUNCH_CHECK();
+  return MP_OK;
+}
+
+int mp_edge_att_alpha_f32(const int32_t* rowptr, const int32_t* col, const int32_t* eid, int64_t N, int64_t nnz,
+                          int32_t heads, const float* a_dst, const float* a_src, const float* a_edge, float slope,
+                          float* alpha, mp_stream_t stream) {
+  if (!rowptr || N < 0 || nnz < 0 || heads < 1 || (nnz > 0 && (!col || !eid || !a_src || !a_edge || !alpha)))
+    return MP_ERR_INVALID_ARG;
+  if (N >= INT32_MAX || nnz >= INT32_MAX) return MP_ERR_UNSUPPORTED;
+  if (N == 0 || nnz == 0) return MP_OK;
+  const AlphaScore<true> sc = {col, eid, a_dst, a_src, a_edge, heads, slope};
+  hipLaunchKernelGGL(gat_alpha_kernel<true>, dim3(flat_grid(N)), dim3(kBlock), 0, as_stream(stream), rowptr, N, sc,
+                     alpha);
   MP_LAUNCH_CHECK();
   return MP_OK;
 }

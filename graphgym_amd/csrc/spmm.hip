@@ -246,7 +246,9 @@ struct XRows {
 // issues two coalesced row loads for it, U entries = 2U row loads in flight.  No per-entry tensor of width d is written or
 // read.  An inserted self loop (eid < 0) has no M term: its load reads row 0 of M (M holds at least one row) and is
 // dropped, so every entry issues the same two loads and the waits stay counted.  T[r] is loaded once when row r starts;
-// on the hub path T[row] is inside every term of a piece, so the partials need no fix-up.  fp32, one head, no marks.
+// on the hub path T[row] is inside every term of a piece, so the partials need no fix-up.  fp32, no marks.  Under NH > 1
+// (edge-feature attention, attconv.py:342-360) the entry's NH weights meet the summed message exactly as they meet X[col]
+// in the one-gather form: the walk hands consume() the weight of the lane's head.
 struct EdgeOperands {
   const int32_t* eid;
   const float* M; int64_t ldm;
@@ -484,23 +486,40 @@ __global__ __launch_bounds__(kBlock) void agg_hub_finalize_kernel(AggArgs<E> a) 
   }
 }
 
+// The head c / hw of a lane's column c = lane, lane + 64, ...: one division per thread, then a step of 64 columns is
+// 64 / hw heads and 64 % hw columns further, with at most one carry (both remainders are below hw).
+struct HeadOfColumn {
+  int h, rem, dh, drem, hw;
+  __device__ __forceinline__ HeadOfColumn(int lane, int hw_)
+      : h(lane / hw_), rem(lane % hw_), dh(kWave / hw_), drem(kWave % hw_), hw(hw_) {}
+  __device__ __forceinline__ void step() {
+    h += dh;
+    rem += drem;
+    if (rem >= hw) { rem -= hw; h += 1; }
+  }
+};
+
 // Backward of the two-gather form into M, sum / mean: dM[eid_e] = val_e (/ deg) * dY[row_e].  One wave per 64 stored
 // entries (balanced whatever the degrees): the row of the first entry by a binary search over rowptr, later rows by
 // walking it; every entry writes one whole row of dM, an input edge belongs to at most one entry — plain stores.
+// HEADS: val is [nnz, heads] and column c takes the weight of its head c / hw (mp_spmm_edge_heads_bwd_f32).
+template <bool HEADS>
 __global__ __launch_bounds__(kBlock) void edge_bwd_rows_kernel(const int32_t* __restrict__ rowptr,
                                                                const int32_t* __restrict__ eid,
-                                                               const float* __restrict__ val, int32_t N, int32_t nnz,
+                                                               const float* __restrict__ val, int32_t heads, int32_t hw,
+                                                               int32_t N, int32_t nnz,
                                                                int mean, const float* __restrict__ dY, int64_t ldy,
                                                                int32_t d, float* __restrict__ dM, int64_t ldm) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int64_t n_chunk = ((int64_t)nnz + kWave - 1) / kWave;
+  const HeadOfColumn hc(lane, HEADS ? hw : 1);
   for (int64_t ch = (int64_t)blockIdx.x * kWavesPerBlock + wave; ch < n_chunk; ch += (int64_t)gridDim.x * kWavesPerBlock) {
     const int ec = (int)(ch * kWave);
     const int n = min(kWave, nnz - ec);
     const int me = min(ec + lane, nnz - 1);
     const int ev = eid[me];
-    const float wv = val ? val[me] : 1.f;
+    const float wv = (!HEADS && val) ? val[me] : 1.f;
     int lo = 0, hi = N;                    // the row r with rowptr[r] <= ec < rowptr[r + 1]
     while (lo < hi) {
       const int mid = lo + ((hi - lo) >> 1);
@@ -513,30 +532,48 @@ __global__ __launch_bounds__(kBlock) void edge_bwd_rows_kernel(const int32_t* __
       while (e >= rend) { r += 1; rend = rowptr[r + 1]; }
       const int ei = bcast_i(ev, j);
       if (ei < 0) continue;
-      float w = bcast_f(wv, j);
-      if (mean) w /= (float)(rend - rowptr[r]);
       const float* __restrict__ g = dY + (int64_t)r * ldy;
       float* __restrict__ o = dM + (int64_t)ei * ldm;
-      for (int c = lane; c < d; c += kWave) o[c] = w * g[c];
+      if constexpr (HEADS) {
+        const float cnt = (float)(rend - rowptr[r]);
+        const float* __restrict__ wh = val + (int64_t)e * heads;
+        HeadOfColumn k = hc;
+        for (int c = lane; c < d; c += kWave, k.step()) {
+          float w = wh[k.h];
+          if (mean) w /= cnt;
+          o[c] = w * g[c];
+        }
+      } else {
+        float w = bcast_f(wv, j);
+        if (mean) w /= (float)(rend - rowptr[r]);
+        for (int c = lane; c < d; c += kWave) o[c] = w * g[c];
+      }
     }
   }
 }
 
 // ... max: dM[eid[e], c] = val[e] * dY[r, c] for e = argmax[r, c] >= 0.  One wave per output row, lanes across columns;
-// a column of a row has one winner and an input edge one entry, so every target is written at most once.
+// a column of a row has one winner and an input edge one entry, so every target is written at most once.  HEADS: as above.
+template <bool HEADS>
 __global__ __launch_bounds__(kBlock) void edge_bwd_max_kernel(const int32_t* __restrict__ eid,
-                                                              const float* __restrict__ val,
+                                                              const float* __restrict__ val, int32_t heads, int32_t hw,
                                                               const int32_t* __restrict__ argmax, int64_t N,
                                                               const float* __restrict__ dY, int64_t ldy, int32_t d,
                                                               float* __restrict__ dM, int64_t ldm) {
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
+  const HeadOfColumn hc(lane, HEADS ? hw : 1);
   for (int64_t r = (int64_t)blockIdx.x * kWavesPerBlock + wave; r < N; r += (int64_t)gridDim.x * kWavesPerBlock) {
-    for (int c = lane; c < d; c += kWave) {
+    HeadOfColumn k = hc;
+    for (int c = lane; c < d; c += kWave, k.step()) {
       const int e = argmax[r * d + c];
       if (e < 0) continue;
       const int ei = eid[e];
-      if (ei >= 0) dM[(int64_t)ei * ldm + c] = (val ? val[e] : 1.f) * dY[r * ldy + c];
+      if (ei < 0) continue;
+      float w;
+      if constexpr (HEADS) w = val[(int64_t)e * heads + k.h];
+      else w = val ? val[e] : 1.f;
+      dM[(int64_t)ei * ldm + c] = w * dY[r * ldy + c];
     }
   }
 }
@@ -671,44 +708,70 @@ static int launch_agg(const typename S::Args& g, const int32_t* counts, hipStrea
   return MP_OK;
 }
 
-template <class S>
+// NH > 1: every entry carries NH weights (val [nnz, NH], required; no second branch).  Mean and max take the same body:
+// mean divides by the row's entry count in finish_row, max keeps the first winning entry per column (argmax, merged
+// across hub pieces in piece order by the finalize kernel).
+template <class S, int NH = 1>
 static int dispatch_reduce(const typename S::Args& g, const int32_t* counts, int reduce, hipStream_t st) {
   const auto& a = S::agg(g);
-  const bool weighted = a.val != nullptr;
-  if constexpr (S::kMarks) {
-    if (a.Q != nullptr) {
-      return weighted ? launch_agg<S, MP_SUM, true, true>(g, counts, st)
-                      : launch_agg<S, MP_SUM, false, true>(g, counts, st);
+  if constexpr (NH > 1) {
+    switch (reduce) {
+      case MP_SUM: return launch_agg<S, MP_SUM, true, false, NH>(g, counts, st);
+      case MP_MEAN: return launch_agg<S, MP_MEAN, true, false, NH>(g, counts, st);
+      case MP_MAX: return launch_agg<S, MP_MAX, true, false, NH>(g, counts, st);
+    }
+    return MP_ERR_INVALID_ARG;
+  } else {
+    const bool weighted = a.val != nullptr;
+    if constexpr (S::kMarks) {
+      if (a.Q != nullptr) {
+        return weighted ? launch_agg<S, MP_SUM, true, true>(g, counts, st)
+                        : launch_agg<S, MP_SUM, false, true>(g, counts, st);
+      }
+    }
+    switch (reduce) {
+      case MP_SUM:
+        return weighted ? launch_agg<S, MP_SUM, true, false>(g, counts, st)
+                        : launch_agg<S, MP_SUM, false, false>(g, counts, st);
+      case MP_MEAN:
+        return weighted ? launch_agg<S, MP_MEAN, true, false>(g, counts, st)
+                        : launch_agg<S, MP_MEAN, false, false>(g, counts, st);
+      case MP_MAX:
+        return weighted ? launch_agg<S, MP_MAX, true, false>(g, counts, st)
+                        : launch_agg<S, MP_MAX, false, false>(g, counts, st);
+    }
+    return MP_ERR_INVALID_ARG;
+  }
+}
+
+// the head count: one weight per entry, or 2 / 4 / 8 of them in one launch (fp32 sources)
+template <class S>
+static int dispatch_heads(const typename S::Args& g, const int32_t* counts, int reduce, int heads, hipStream_t st) {
+  if (heads <= 1) return dispatch_reduce<S>(g, counts, reduce, st);
+  if constexpr (S::E::kExtras) {
+    switch (heads) {
+      case 2: return dispatch_reduce<S, 2>(g, counts, reduce, st);
+      case 4: return dispatch_reduce<S, 4>(g, counts, reduce, st);
+      case 8: return dispatch_reduce<S, 8>(g, counts, reduce, st);
     }
   }
-  switch (reduce) {
-    case MP_SUM:
-      return weighted ? launch_agg<S, MP_SUM, true, false>(g, counts, st)
-                      : launch_agg<S, MP_SUM, false, false>(g, counts, st);
-    case MP_MEAN:
-      return weighted ? launch_agg<S, MP_MEAN, true, false>(g, counts, st)
-                      : launch_agg<S, MP_MEAN, false, false>(g, counts, st);
-    case MP_MAX:
-      return weighted ? launch_agg<S, MP_MAX, true, false>(g, counts, st)
-                      : launch_agg<S, MP_MAX, false, false>(g, counts, st);
-  }
-  return MP_ERR_INVALID_ARG;
+  return MP_ERR_UNSUPPORTED;
 }
 
 // the source: two gathers when the call brings the operands of the two-gather form (fp32 only), else one
 template <class E, int W>
-static int dispatch_source(const AggArgs<E>& a, const EdgeOperands* eo, const int32_t* counts, int reduce,
+static int dispatch_source(const AggArgs<E>& a, const EdgeOperands* eo, const int32_t* counts, int reduce, int heads,
                            hipStream_t st) {
   if (eo) {
     if constexpr (std::is_same<E, F32>::value) {
       const EdgeArgs g = {a, *eo};
-      return eo->T ? dispatch_reduce<EdgeRows<W, true>>(g, counts, reduce, st)
-                   : dispatch_reduce<EdgeRows<W, false>>(g, counts, reduce, st);
+      return eo->T ? dispatch_heads<EdgeRows<W, true>>(g, counts, reduce, heads, st)
+                   : dispatch_heads<EdgeRows<W, false>>(g, counts, reduce, heads, st);
     } else {
       return MP_ERR_UNSUPPORTED;
     }
   }
-  return dispatch_reduce<XRows<E, W>>(a, counts, reduce, st);
+  return dispatch_heads<XRows<E, W>>(a, counts, reduce, heads, st);
 }
 
 static bool aligned(const void* p, size_t a) { return p == nullptr || ((uintptr_t)p % a) == 0; }
@@ -798,36 +861,14 @@ static int agg_common(const int32_t* rowptr, const int32_t* col, const float* va
 
   const int w = pick_width(a, eo);
   if (l2norm && d > kWave * w) return MP_ERR_UNSUPPORTED;   // the row must sit in one wave
-  if constexpr (E::kExtras) {
-    if (heads > 1) {
-      if (!val || Q || d % heads) return MP_ERR_INVALID_ARG;
-      // mean and max take the same body: mean divides by the row's entry count in finish_row, max keeps the first
-      // winning entry per column (argmax, merged across hub pieces in piece order by the finalize kernel)
-#define MP_HEADS_R(WV, R)                                                                      \
-      switch (heads) {                                                                         \
-        case 2: return launch_agg<XRows<E, WV>, R, true, false, 2>(a, counts, st);               \
-        case 4: return launch_agg<XRows<E, WV>, R, true, false, 4>(a, counts, st);               \
-        case 8: return launch_agg<XRows<E, WV>, R, true, false, 8>(a, counts, st);               \
-        default: return MP_ERR_UNSUPPORTED;                                                    \
-      }
-#define MP_HEADS(WV)                                                                           \
-      switch (reduce) {                                                                        \
-        case MP_SUM: MP_HEADS_R(WV, MP_SUM)                                                    \
-        case MP_MEAN: MP_HEADS_R(WV, MP_MEAN)                                                  \
-        default: MP_HEADS_R(WV, MP_MAX)                                                        \
-      }
-      if (w == 4) { MP_HEADS(4) } else if (w == 2) { MP_HEADS(2) } else { MP_HEADS(1) }
-#undef MP_HEADS
-#undef MP_HEADS_R
-    }
-  }
+  if (heads > 1 && (!E::kExtras || !val || Q || d % heads)) return MP_ERR_INVALID_ARG;
   if constexpr (E::kMaxW == 8) {
-    if (w == 8) return dispatch_source<E, 8>(a, eo, counts, reduce, st);
+    if (w == 8) return dispatch_source<E, 8>(a, eo, counts, reduce, heads, st);
   }
   switch (w) {
-    case 4: return dispatch_source<E, 4>(a, eo, counts, reduce, st);
-    case 2: return dispatch_source<E, 2>(a, eo, counts, reduce, st);
-    default: return dispatch_source<E, 1>(a, eo, counts, reduce, st);
+    case 4: return dispatch_source<E, 4>(a, eo, counts, reduce, heads, st);
+    case 2: return dispatch_source<E, 2>(a, eo, counts, reduce, heads, st);
+    default: return dispatch_source<E, 1>(a, eo, counts, reduce, heads, st);
   }
 }
 
@@ -999,27 +1040,65 @@ int mp_spmm_csr_edge_f32(const int32_t* rowptr, const int32_t* col, const int32_
                          nullptr, 0, 1e-12f, 1, &eo);
 }
 
-int mp_spmm_edge_bwd_f32(const int32_t* rowptr, const int32_t* eid, const float* val, const int32_t* argmax, int64_t N,
-                         int64_t nnz, int reduce, const float* dY, int64_t ldy, int32_t d, float* dM, int64_t ldm,
-                         mp_stream_t stream) {
+int mp_spmm_csr_edge_heads_f32(const int32_t* rowptr, const int32_t* col, const int32_t* eid, const float* a, int64_t N,
+                               const int32_t* plan, const int32_t* counts_host, int32_t heads, const float* X,
+                               int64_t ldx, const float* M, int64_t ldm, const float* T, int64_t ldt, float* Y,
+                               int64_t ldy, int32_t d, int reduce, const float* bias, int32_t* argmax, void* ws,
+                               size_t ws_bytes, mp_stream_t stream) {
+  if (!col || !eid || !a || !M || heads < 1 || d <= 0 || d % heads || ldm < d || (T && ldt < d))
+    return MP_ERR_INVALID_ARG;
+  if (heads != 1 && heads != 2 && heads != 4 && heads != 8) return MP_ERR_UNSUPPORTED;
+  const EdgeOperands eo = {eid, M, ldm, T, T ? ldt : 0};
+  return agg_common<F32>(rowptr, col, a, N, plan, counts_host, X, ldx, Y, ldy, nullptr, 0, d, reduce, nullptr, 0, 0.f,
+                         bias, MP_ACT_NONE, reduce == MP_MAX ? argmax : nullptr, ws, ws_bytes, as_stream(stream),
+                         nullptr, 0, 1e-12f, heads, &eo);
+}
+
+// the two backward launches into M: one weight per entry (heads <= 1; val may be NULL) or val [nnz, heads]
+static int edge_bwd_launch(const int32_t* rowptr, const int32_t* eid, const float* val, int32_t heads,
+                           const int32_t* argmax, int64_t N, int64_t nnz, int reduce, const float* dY, int64_t ldy,
+                           int32_t d, float* dM, int64_t ldm, hipStream_t st) {
   if (!rowptr || !eid || !dY || !dM || N < 0 || nnz < 0 || d < 1) return MP_ERR_INVALID_ARG;
   if (reduce < MP_SUM || reduce > MP_MAX || (reduce == MP_MAX && !argmax)) return MP_ERR_INVALID_ARG;
   if (ldy < d || ldm < d) return MP_ERR_INVALID_ARG;
   if (N >= INT32_MAX || nnz >= INT32_MAX) return MP_ERR_UNSUPPORTED;
   if (N == 0 || nnz == 0) return MP_OK;
+  const int32_t hw = heads > 1 ? d / heads : d;
   if (reduce == MP_MAX) {
     int64_t blocks = ceil_div(N, kWavesPerBlock);
     if (blocks > kNumCU * 16) blocks = kNumCU * 16;
-    hipLaunchKernelGGL(edge_bwd_max_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), eid, val,
-                       argmax, N, dY, ldy, d, dM, ldm);
+    if (heads > 1)
+      hipLaunchKernelGGL(edge_bwd_max_kernel<true>, dim3((unsigned)blocks), dim3(kBlock), 0, st, eid, val, heads, hw,
+                         argmax, N, dY, ldy, d, dM, ldm);
+    else
+      hipLaunchKernelGGL(edge_bwd_max_kernel<false>, dim3((unsigned)blocks), dim3(kBlock), 0, st, eid, val, 1, hw,
+                         argmax, N, dY, ldy, d, dM, ldm);
   } else {
     int64_t blocks = ceil_div(ceil_div(nnz, kWave), kWavesPerBlock);
     if (blocks > kNumCU * 16) blocks = kNumCU * 16;
-    hipLaunchKernelGGL(edge_bwd_rows_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), rowptr, eid,
-                       val, (int32_t)N, (int32_t)nnz, reduce == MP_MEAN ? 1 : 0, dY, ldy, d, dM, ldm);
+    const int mean = reduce == MP_MEAN ? 1 : 0;
+    if (heads > 1)
+      hipLaunchKernelGGL(edge_bwd_rows_kernel<true>, dim3((unsigned)blocks), dim3(kBlock), 0, st, rowptr, eid, val,
+                         heads, hw, (int32_t)N, (int32_t)nnz, mean, dY, ldy, d, dM, ldm);
+    else
+      hipLaunchKernelGGL(edge_bwd_rows_kernel<false>, dim3((unsigned)blocks), dim3(kBlock), 0, st, rowptr, eid, val, 1,
+                         hw, (int32_t)N, (int32_t)nnz, mean, dY, ldy, d, dM, ldm);
   }
   MP_LAUNCH_CHECK();
   return MP_OK;
+}
+
+int mp_spmm_edge_bwd_f32(const int32_t* rowptr, const int32_t* eid, const float* val, const int32_t* argmax, int64_t N,
+                         int64_t nnz, int reduce, const float* dY, int64_t ldy, int32_t d, float* dM, int64_t ldm,
+                         mp_stream_t stream) {
+  return edge_bwd_launch(rowptr, eid, val, 1, argmax, N, nnz, reduce, dY, ldy, d, dM, ldm, as_stream(stream));
+}
+
+int mp_spmm_edge_heads_bwd_f32(const int32_t* rowptr, const int32_t* eid, const float* a, int32_t heads,
+                               const int32_t* argmax, int64_t N, int64_t nnz, int reduce, const float* dY, int64_t ldy,
+                               int32_t d, float* dM, int64_t ldm, mp_stream_t stream) {
+  if (!a || heads < 1 || d < 1 || d % heads) return MP_ERR_INVALID_ARG;
+  return edge_bwd_launch(rowptr, eid, a, heads, argmax, N, nnz, reduce, dY, ldy, d, dM, ldm, as_stream(stream));
 }
 
 int mp_spmm_max_bwd_f32(const int32_t* col, const float* val, const int32_t* argmax, const float* dY,

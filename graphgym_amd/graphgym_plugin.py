@@ -12,13 +12,16 @@ Importing this module is the whole integration:
   * the design-space attention keys 'gaddconv', 'gmulconv' (graphgym/contrib/layer/attconv.py:239-240),
     installed by install_design() — kept apart from ALL_KEYS, the ID-GNN path's keys that install() returns,
   * the built-in edge-feature keys 'generaledgeconv', 'generalsampleedgeconv' (graphgym/models/layer.py:233-234),
-    installed by install_edge() — a third dictionary, EDGE_KEYS, for the same reason.
+    installed by install_edge() — a third dictionary, EDGE_KEYS, for the same reason,
+  * the edge-feature attention keys 'generaledgeattconvv1', 'generaledgeattconvv2'
+    (graphgym/contrib/layer/attconv.py:542-543), installed by install_edge_att() — a fourth dictionary, EDGE_ATT_KEYS.
 
 ``register_layer`` raises KeyError on a duplicate (register.py:6-10), and built-ins shadow
 registered keys (layer.py:238), so taking over an existing key is done by assignment into the
 dictionaries — ``install(override=True)``, the default.
 """
 from . import attconv as A
+from . import edgeattconv as EA
 from . import edgeconv as EC
 from . import layers as L
 from . import registry as R
@@ -55,6 +58,10 @@ DESIGN_KEYS = {
 EDGE_KEYS = {
     'generaledgeconv': EC.GeneralEdgeConv,
     'generalsampleedgeconv': EC.GeneralSampleEdgeConv,
+}
+EDGE_ATT_KEYS = {
+    'generaledgeattconvv1': EA.GeneralEdgeAttConvv1,
+    'generaledgeattconvv2': EA.GeneralEdgeAttConvv2,
 }
 
 
@@ -102,9 +109,15 @@ def install_edge(override=True):
     return _install_keys(EDGE_KEYS, override)
 
 
+def install_edge_att(override=True):
+    """Register the edge-feature attention keys of EDGE_ATT_KEYS with install()'s semantics; returns the keys taken."""
+    return _install_keys(EDGE_ATT_KEYS, override)
+
+
 installed_keys = install(override=True)
 installed_design_keys = install_design(override=True)
 installed_edge_keys = install_edge(override=True)
+installed_edge_att_keys = install_edge_att(override=True)
 
 
 # ---- the post-ops of GraphGym's layer wrapper on the engine -------------------------------------------------

@@ -6,6 +6,7 @@ C-ABI entry point of libmpengine.so (include/mp_engine.h).
     index_add_rows(h, id, u)     tensor_scatter_nd_add / index_add_ (K10)
     edge_softmax / sddmm_*       GAT pieces (TfgIDLayer.py:333-355; idconv.py:317-332)
     spmm_edge(g, x, m, reduce)   aggregation of messages with an edge feature (generalconv.py:203-209)
+    edge_att_alpha / spmm_edge_heads   attention over messages with an edge feature (attconv.py:342-360)
 """
 import ctypes as C
 import os
@@ -526,14 +527,17 @@ def gather_rows(x, ids):
 
 # ---- attention pieces --------------------------------------------------------
 
-def _raw_sddmm_dot(g, A, B, heads, scale):
+def _raw_sddmm_dot(g, A, B, heads, scale, idx=None):
+    """s[e, h] = scale * <A[row_e, slice h], B[idx[e], slice h]>; idx [nnz] int32: the row of B an entry reads (default:
+    its column, g.col)"""
     L = lib()
+    idx = g.col if idx is None else idx
     s = torch.empty(max(g.nnz, 1) * heads, dtype=torch.float32, device=A.device)
     with torch.cuda.device(A.device):
-        st = L.mp_sddmm_dot_stream_f32(ptr(g.row_ids()), ptr(g.col), g.nnz, ptr(A), A.stride(0), ptr(B),
+        st = L.mp_sddmm_dot_stream_f32(ptr(g.row_ids()), ptr(idx), g.nnz, ptr(A), A.stride(0), ptr(B),
                                        B.stride(0), A.size(1), heads, float(scale), ptr(s), _stream())
         if st == 2:   # head layout the entry-balanced kernel does not cover
-            st = L.mp_sddmm_dot_f32(ptr(g.rowptr), ptr(g.col), g.num_nodes, g.nnz, ptr(A), A.stride(0),
+            st = L.mp_sddmm_dot_f32(ptr(g.rowptr), ptr(idx), g.num_nodes, g.nnz, ptr(A), A.stride(0),
                                     ptr(B), B.stride(0), A.size(1), heads, float(scale), ptr(s), _stream())
         check(st, "mp_sddmm_dot")
     return s[:g.nnz * heads].view(g.nnz, heads)
@@ -757,14 +761,16 @@ def _raw_spmm_heads_reduce(g, a, V, heads, reduce):
     return y, argmax
 
 
-def _raw_heads_max_da(g, argmax, dy, V, heads):
+def _raw_heads_max_da(g, argmax, dy, V, heads, idx=None):
     """da[e, h] = sum over the columns c of head h that entry e won (argmax[row_e, c] == e) of dy[row_e, c] V[col_e, c]
-    (mp_spmm_heads_max_da_f32; head layouts it does not take: per head on column slices)"""
+    (mp_spmm_heads_max_da_f32; head layouts it does not take: per head on column slices).  idx [nnz] int32: the row of V
+    an entry reads in the place of its column"""
     L = lib()
     nnz, d = g.nnz, V.size(1)
+    idx = g.col if idx is None else idx
     da = torch.empty((max(nnz, 1), heads), dtype=torch.float32, device=V.device)
     with torch.cuda.device(V.device):
-        st = L.mp_spmm_heads_max_da_f32(ptr(g.row_ids()), ptr(g.col), nnz, ptr(argmax), argmax.stride(0), ptr(dy),
+        st = L.mp_spmm_heads_max_da_f32(ptr(g.row_ids()), ptr(idx), nnz, ptr(argmax), argmax.stride(0), ptr(dy),
                                         dy.stride(0), ptr(V), V.stride(0), d, heads, ptr(da), _stream())
         if st != 2:
             check(st, "mp_spmm_heads_max_da_f32")
@@ -773,7 +779,7 @@ def _raw_heads_max_da(g, argmax, dy, V, heads):
         one = torch.empty(max(nnz, 1), dtype=torch.float32, device=V.device)
         for h in range(heads):
             cs = slice(h * dh, (h + 1) * dh)
-            check(L.mp_spmm_heads_max_da_f32(ptr(g.row_ids()), ptr(g.col), nnz, ptr(argmax[:, cs]), argmax.stride(0),
+            check(L.mp_spmm_heads_max_da_f32(ptr(g.row_ids()), ptr(idx), nnz, ptr(argmax[:, cs]), argmax.stride(0),
                                              ptr(dy[:, cs]), dy.stride(0), ptr(V[:, cs]), V.stride(0), dh, 1, ptr(one),
                                              _stream()), "mp_spmm_heads_max_da_f32")
             da[:, h] = one
@@ -849,6 +855,8 @@ def spmm_edge_values(g, a, V, heads=1, reduce="sum"):
 #   mp::dense_fused     act(P W [+ Q W_id] + b)                        the transform after the aggregation
 #   mp::bn_act          BatchNorm1d (training statistics) [+ ReLU]     graphgym/models/layer.py:26-35
 #   mp::spmm_edge       y = reduce_e w_e (x_j + m_e + t_i) + b         GeneralEdgeConvLayer.message, generalconv.py:203-209
+#   mp::edge_att_alpha  softmax_i lrelu(a_dst_i + a_src_j + a_edge_e)  GeneralEdgeAttConvv1Layer.message, attconv.py:352-357
+#   mp::spmm_edge_heads y = reduce_e w_eh (x_j + m_e + t_i)^h + b      ... attconv.py:358-360
 # =========================================================================================
 from typing import Optional, Tuple   # noqa: E402
 
@@ -1564,3 +1572,337 @@ def spmm_edge(g, x, m, reduce="sum", t=None, bias=None):
                                 "and generalsampleedgeconv have no bfloat16 or float16 form)")
     _eid_checked(g, m.size(0))
     return torch.ops.mp.spmm_edge(x, m, t, bias, g.handle, _lib.REDUCE[reduce])[0]
+
+
+# ---- attention over messages with an edge feature (attconv.py:342-360) ----------------------------------------------
+def _edge_att_f32(t, name, op):
+    """an operand of edge_att_alpha / spmm_edge_heads: float32 only, rows unit-stride"""
+    _require_hip(t, name)
+    if t.dtype != torch.float32:
+        raise TypeError(f"{op} is float32 only: {name} is {t.dtype} (the edge-feature attention keys "
+                        "generaledgeattconvv1 and generaledgeattconvv2 have no bfloat16 or float16 form)")
+    return t if t.dim() == 2 and t.stride(1) == 1 else t.contiguous()
+
+
+def _eid_clamped(g):
+    """g.eid with the inserted loops (eid < 0) pointed at row 0, and the mask of the entries that have an input edge (None:
+    all of them); cached on g"""
+    hit = g.__dict__.get("_eid_clamped")
+    if hit is None:
+        eid = g.eid
+        if g.nnz and bool((eid < 0).any()):
+            hit = (eid.clamp(min=0).contiguous(), eid >= 0)
+        else:
+            hit = (eid, None)
+        g.__dict__["_eid_clamped"] = hit
+    return hit
+
+
+@custom_op("mp::edge_att_alpha", mutates_args=(), device_types="cuda")
+def _op_edge_att_alpha(a_dst: Optional[Tensor], a_src: Tensor, a_edge: Tensor, graph: int, slope: float) -> Tensor:
+    g = from_handle(graph)
+    asr = _edge_att_f32(a_src, "a_src", "edge_att_alpha").contiguous()
+    aed = _edge_att_f32(a_edge, "a_edge", "edge_att_alpha").contiguous()
+    ad = None if a_dst is None else _edge_att_f32(a_dst, "a_dst", "edge_att_alpha").contiguous()
+    H = asr.size(1)
+    if asr.size(0) != g.num_cols or aed.size(1) != H or (ad is not None and tuple(ad.shape) != (g.num_nodes, H)):
+        raise ValueError(f"a_src is {tuple(asr.shape)}, a_edge {tuple(aed.shape)}, a_dst "
+                         f"{None if ad is None else tuple(ad.shape)}: expected [{g.num_cols}, H], [E, H], "
+                         f"[{g.num_nodes}, H]")
+    eid = _eid_checked(g, aed.size(0))
+    if aed.size(0) == 0:      # every entry is an inserted loop: nothing reads it, the kernel wants an address
+        aed = torch.zeros((1, H), dtype=torch.float32, device=asr.device)
+    alpha = torch.empty((g.nnz, H), dtype=torch.float32, device=asr.device)
+    with torch.cuda.device(asr.device):
+        check(lib().mp_edge_att_alpha_f32(ptr(g.rowptr), ptr(g.col), ptr(eid), g.num_nodes, g.nnz, H, ptr(ad), ptr(asr),
+                                          ptr(aed), float(slope), ptr(alpha), _stream()), "mp_edge_att_alpha_f32")
+    return alpha
+
+
+@_op_edge_att_alpha.register_fake
+def _(a_dst, a_src, a_edge, graph, slope):
+    return a_src.new_empty((from_handle(graph).nnz, a_src.size(1)))
+
+
+_EA_DST, _EA_SRC, _EA_EDGE = 1, 2, 4
+
+
+@custom_op("mp::edge_att_alpha_bwd_raw", mutates_args=(), device_types="cuda")
+def _op_edge_att_alpha_bwd_raw(dalpha: Tensor, alpha: Tensor, a_dst: Optional[Tensor], a_src: Tensor, a_edge: Tensor,
+                               graph: int, slope: float, want: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """(d_dst, d_src, d_edge) of edge_att_alpha, each computed when its bit of `want` (1, 2, 4) is set and empty
+    otherwise: the row softmax backward (mp_csr_row_softmax_bwd_f32), the slope mask on the recomputed pre-activation,
+    sums by destination and by source; an input edge belongs to at most one entry, so d_edge is an indexed store into
+    zeros"""
+    g = from_handle(graph)
+    H = alpha.size(1)
+    alpha, dalpha = alpha.contiguous(), dalpha.contiguous()
+    ds = torch.empty_like(alpha)
+    if g.nnz:
+        with torch.cuda.device(alpha.device):
+            check(lib().mp_csr_row_softmax_bwd_f32(ptr(g.rowptr), g.num_nodes, H, ptr(alpha), ptr(dalpha), ptr(ds),
+                                                   _stream()), "mp_csr_row_softmax_bwd_f32")
+    rows, cols = g.row_ids().long(), g.col.long()
+    eidc, has = _eid_clamped(g)
+    eidc = eidc.long()
+    pre = a_src[cols] if a_dst is None else a_dst[rows] + a_src[cols]
+    if a_edge.size(0):
+        ae = a_edge[eidc]
+        pre = pre + (ae if has is None else torch.where(has[:, None], ae, torch.zeros_like(ae)))
+    ds = ds * torch.where(pre > 0, torch.ones_like(pre), torch.full_like(pre, slope))
+    d_dst, d_src, d_edge = (_empty_like_none(alpha) for _ in range(3))     # (returns of a custom op may not alias)
+    if want & _EA_DST and a_dst is not None:
+        d_dst = torch.zeros_like(a_dst).index_add_(0, rows, ds)
+    if want & _EA_SRC:
+        d_src = torch.zeros_like(a_src).index_add_(0, cols, ds)
+    if want & _EA_EDGE:
+        d_edge = torch.zeros_like(a_edge)
+        if a_edge.size(0):
+            if has is None:
+                d_edge[eidc] = ds
+            else:
+                d_edge[eidc[has]] = ds[has]
+    return d_dst, d_src, d_edge
+
+
+@_op_edge_att_alpha_bwd_raw.register_fake
+def _(dalpha, alpha, a_dst, a_src, a_edge, graph, slope, want):
+    e = lambda on, shape: alpha.new_empty(shape if on else (0,))      # noqa: E731
+    return (e(want & _EA_DST and a_dst is not None, a_src.shape if a_dst is None else a_dst.shape),
+            e(want & _EA_SRC, a_src.shape), e(want & _EA_EDGE, a_edge.shape))
+
+
+def _edge_att_alpha_setup(ctx, inputs, output):
+    a_dst, a_src, a_edge, graph, slope = inputs
+    ctx.graph, ctx.slope, ctx.g_alive = graph, slope, from_handle(graph)
+    ctx.has_dst = a_dst is not None
+    ctx.save_for_backward(output, a_dst, a_src, a_edge)
+
+
+def _edge_att_alpha_backward(ctx, dalpha):
+    alpha, a_dst, a_src, a_edge = ctx.saved_tensors
+    need = ctx.needs_input_grad
+    want = (_EA_DST if (ctx.has_dst and need[0]) else 0) | (_EA_SRC if need[1] else 0) | (_EA_EDGE if need[2] else 0)
+    if not want:
+        return (None,) * 5
+    d_dst, d_src, d_edge = torch.ops.mp.edge_att_alpha_bwd_raw(dalpha, alpha, a_dst, a_src, a_edge, ctx.graph, ctx.slope,
+                                                               want)
+    return (d_dst if want & _EA_DST else None, d_src if want & _EA_SRC else None, d_edge if want & _EA_EDGE else None,
+            None, None)
+
+
+register_autograd("mp::edge_att_alpha", _edge_att_alpha_backward, setup_context=_edge_att_alpha_setup)
+
+
+def edge_att_alpha(g, a_dst, a_src, a_edge, slope=0.2):
+    """alpha[e, h] = softmax over the entries of e's destination row of leaky_relu(a_dst[row_e, h] + a_src[col_e, h] +
+    a_edge[eid_e, h])   (torch.ops.mp.edge_att_alpha) -> [nnz, H]
+
+    The attention coefficients of GeneralEdgeAttConvv1Layer / v2 (attconv.py:352-357): a_src [n, H] by source, a_edge
+    [E, H] by the entry's position in the input edge_index (g.eid; an inserted self loop has no edge term), a_dst [N, H]
+    by destination or None.  One launch for all heads, the scores are never stored.  float32 only; differentiable in
+    all three."""
+    for name, v in (("a_dst", a_dst), ("a_src", a_src), ("a_edge", a_edge)):
+        if v is not None:
+            _edge_att_f32(v, name, "edge_att_alpha")
+    _eid_checked(g, a_edge.size(0))
+    return torch.ops.mp.edge_att_alpha(a_dst, a_src, a_edge, g.handle, float(slope))
+
+
+SPMM_EDGE_HEADS_ONE_LAUNCH = (2, 4, 8)     # head counts of mp_spmm_csr_edge_heads_f32 beside 1
+
+
+def _raw_spmm_edge_heads(g, w, x, m, t=None, bias=None, heads=1, reduce=_lib.SUM, want_argmax=False, one_launch=True):
+    """y[r, slice h] = reduce_e w[e, h] (x[col_e] + m[eid_e] + t[r])[slice h] + bias -> (y, argmax [N, d] int32 or None):
+    mp_spmm_csr_edge_f32 with val = w for one head, mp_spmm_csr_edge_heads_f32 for 2, 4 or 8 heads at once, and for
+    every other head count one launch of mp_spmm_csr_edge_f32 per head on column slices.  one_launch=False sends 2, 4 and
+    8 heads through the per-head form too (tests, tests/perf/bench_edgeatt.py): the same terms in the same order, the
+    same bits, and the slower form as this function runs it — by 1.5 % on 2e7 entries, where the copies of w's columns cost more
+    than the H launches save, and threefold on 2e5 entries.  The entry values of g take no part: they
+    belong in w."""
+    L = lib()
+    N, d = g.num_nodes, x.size(1)
+    eid = _eid_checked(g, m.size(0))
+    g.plan()                                     # built once, shared by the per-head graphs below
+    if heads == 1:
+        return _raw_spmm_edge(g.with_values(w.reshape(-1)), x, m, t, bias, reduce, want_argmax)
+    if m.size(0) == 0:
+        m = torch.zeros((1, d), dtype=torch.float32, device=x.device)
+    y = placement.empty_or_torch((N, d), x.device, reads=(x, m))
+    argmax = torch.empty((N, d), dtype=torch.int32, device=x.device) if want_argmax else None
+    if one_launch and heads in SPMM_EDGE_HEADS_ONE_LAUNCH:
+        plan, counts, ws, ws_bytes = _plan_ws(g, x.device, d, reduce, False)
+        with torch.cuda.device(x.device):
+            st = L.mp_spmm_csr_edge_heads_f32(ptr(g.rowptr), ptr(g.col), ptr(eid), ptr(w), N, ptr(plan), counts, heads,
+                                              ptr(x), x.stride(0), ptr(m), m.stride(0), ptr(t),
+                                              t.stride(0) if t is not None else 0, ptr(y), y.stride(0), d, reduce,
+                                              ptr(bias), ptr(argmax), ptr(ws), ws_bytes, _stream())
+        if st != 2:
+            check(st, "mp_spmm_csr_edge_heads_f32")
+            return y, argmax
+    dh = d // heads
+    top = g.__dict__.get("_eid_max")
+    for h in range(heads):
+        cs = slice(h * dh, (h + 1) * dh)
+        gh = g.with_values(w[:, h].contiguous())
+        gh.__dict__["_eid_max"] = top            # (checked on g above: no second read of it per head)
+        _, am = _raw_spmm_edge(gh, x[:, cs], m[:, cs], None if t is None else t[:, cs],
+                               None if bias is None else bias[cs], reduce, want_argmax, out=y[:, cs])
+        if want_argmax:
+            argmax[:, cs] = am
+    return y, argmax
+
+
+@custom_op("mp::spmm_edge_heads", mutates_args=(), device_types="cuda")
+def _op_spmm_edge_heads(w: Tensor, x: Tensor, m: Tensor, t: Optional[Tensor], bias: Optional[Tensor], graph: int,
+                        heads: int, reduce: int) -> Tuple[Tensor, Tensor]:
+    g = from_handle(graph)
+    op = "spmm_edge_heads"
+    x, m = _edge_att_f32(x, "x", op), _edge_att_f32(m, "m", op)
+    t = None if t is None else _edge_att_f32(t, "t", op)
+    if heads < 1 or x.size(1) % heads:
+        raise ValueError(f"x has {x.size(1)} columns, not a multiple of heads = {heads}")
+    # w dense [nnz, H]: the kernels read w[e * H + h], whatever the caller's strides
+    w = _edge_att_f32(w.reshape(g.nnz, heads), "w", op).contiguous()
+    if x.size(0) != g.num_cols or m.size(1) != x.size(1):
+        raise ValueError(f"x is {tuple(x.shape)}, m is {tuple(m.shape)}: the operator has {g.num_cols} columns and both "
+                         "operands share one width")
+    if t is not None and tuple(t.shape) != (g.num_nodes, x.size(1)):
+        raise ValueError(f"t is {tuple(t.shape)}, expected {(g.num_nodes, x.size(1))}")
+    if bias is not None and bias.dtype != torch.float32:
+        raise TypeError(f"spmm_edge_heads is float32 only: bias is {bias.dtype}")
+    y, argmax = _raw_spmm_edge_heads(g, w, x, m, t, None if bias is None else bias.contiguous(), heads, reduce,
+                                     reduce == _lib.MAX)
+    return y, (argmax if argmax is not None else _empty_like_none(x, torch.int32))
+
+
+@_op_spmm_edge_heads.register_fake
+def _(w, x, m, t, bias, graph, heads, reduce):
+    n = from_handle(graph).num_nodes
+    return x.new_empty((n, x.size(1))), x.new_empty((n, x.size(1)) if reduce == _lib.MAX else (0,), dtype=torch.int32)
+
+
+_EH_W, _EH_X, _EH_M, _EH_T = 1, 2, 4, 8
+
+
+@custom_op("mp::spmm_edge_heads_bwd_raw", mutates_args=(), device_types="cuda")
+def _op_spmm_edge_heads_bwd_raw(dy: Tensor, w: Tensor, x: Tensor, m: Tensor, t: Optional[Tensor], argmax: Tensor,
+                                graph: int, heads: int, reduce: int,
+                                want: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(dw, dx, dm, dt) of spmm_edge_heads, each computed when its bit of `want` (1, 2, 4, 8) is set and empty otherwise"""
+    g = from_handle(graph)
+    L = lib()
+    op = "spmm_edge_heads"
+    dy = dy if (dy.dim() == 2 and dy.stride(1) == 1) else dy.contiguous()
+    x, m = _edge_att_f32(x, "x", op), _edge_att_f32(m, "m", op)
+    t = None if t is None else _edge_att_f32(t, "t", op)
+    w = w.reshape(g.nnz, heads).contiguous()
+    N, d = dy.shape
+    hw = d // heads
+    E = m.size(0)
+    is_max = reduce == _lib.MAX
+    dw, dx, dm, dt = (_empty_like_none(dy) for _ in range(4))      # four tensors: returns of a custom op may not alias
+    dy0 = dy
+    if reduce == _lib.MEAN and want & (_EH_W | _EH_X | _EH_T):      # the mean's backward is the sum's on dy / (row entry count)
+        dy = (dy / g.entry_counts().clamp(min=1.0)[:, None]).contiguous()
+    eidc, has = _eid_clamped(g)
+    if want & _EH_X:
+        if is_max:
+            dx = torch.zeros((g.num_cols, d), dtype=torch.float32, device=dy.device)
+            if g.nnz:
+                with torch.cuda.device(dy.device):
+                    check(L.mp_spmm_heads_max_bwd_f32(ptr(g.col), ptr(w), heads, ptr(argmax), N, d, ptr(dy), dy.stride(0),
+                                                      ptr(dx), dx.stride(0), _stream()), "mp_spmm_heads_max_bwd_f32")
+        else:
+            gt = g._transpose_sorted()     # (per-entry values are permuted through gt.pos: also when A^T = A)
+            dx = _raw_spmm_heads(gt, w[gt.pos.long()].contiguous(), dy, heads)
+    if want & _EH_M:
+        dm = torch.zeros((E, d), dtype=torch.float32, device=dy.device)
+        if E and g.nnz:
+            with torch.cuda.device(dy.device):
+                check(L.mp_spmm_edge_heads_bwd_f32(ptr(g.rowptr), ptr(g.eid), ptr(w), heads, ptr(argmax if is_max else None),
+                                                   N, g.nnz, reduce, ptr(dy0), dy0.stride(0), d, ptr(dm), dm.stride(0),
+                                                   _stream()), "mp_spmm_edge_heads_bwd_f32")
+    if want & _EH_T and t is not None:
+        if is_max:     # each column's winner carries t once
+            am = argmax.long()
+            head_of = torch.arange(d, device=dy.device) // hw
+            dt = w.reshape(-1)[(am.clamp(min=0) * heads + head_of)] * dy
+            dt = torch.where(am >= 0, dt, torch.zeros_like(dt))
+        else:          # t[r] rides in every entry of row r: the per-head row sums of w, on the aggregation kernel
+            ones = torch.ones((g.num_cols, heads), dtype=torch.float32, device=dy.device)
+            rs = _raw_spmm_heads(g, w, ones, heads)                        # [N, H]
+            dt = (rs[:, :, None] * dy.view(N, heads, hw)).reshape(N, d)
+    if want & _EH_W:
+        # dw[e, h] = <dy[row_e], x[col_e] + m[eid_e] + t[row_e]>_h: three per-entry dots (max: over the columns e won)
+        if E == 0:
+            m = torch.zeros((1, d), dtype=torch.float32, device=dy.device)
+        if is_max:
+            dw = _raw_heads_max_da(g, argmax, dy, x, heads)
+            dwm = _raw_heads_max_da(g, argmax, dy, m, heads, idx=eidc)
+        else:
+            dw = _raw_sddmm_dot(g, dy, x, heads, 1.0)
+            dwm = _raw_sddmm_dot(g, dy, m, heads, 1.0, idx=eidc)
+        dw = dw + (dwm if has is None else torch.where(has[:, None], dwm, torch.zeros_like(dwm)))
+        if t is not None:
+            if is_max:
+                dw = dw + _raw_heads_max_da(g, argmax, dy, t, heads, idx=g.row_ids())
+            else:
+                dw = dw + (dy.view(N, heads, hw) * t.view(N, heads, hw)).sum(-1)[g.row_ids().long()]
+    return dw, dx, dm, dt
+
+
+@_op_spmm_edge_heads_bwd_raw.register_fake
+def _(dy, w, x, m, t, argmax, graph, heads, reduce, want):
+    e = lambda on, shape: dy.new_empty(shape if on else (0,))      # noqa: E731
+    return (e(want & _EH_W, w.shape), e(want & _EH_X, x.shape), e(want & _EH_M, m.shape),
+            e(want & _EH_T and t is not None, dy.shape))
+
+
+def _spmm_edge_heads_setup(ctx, inputs, output):
+    ctx.set_materialize_grads(False)
+    w, x, m, t, bias, graph, heads, reduce = inputs
+    ctx.graph, ctx.heads, ctx.reduce = graph, heads, reduce
+    ctx.g_alive = from_handle(graph)
+    ctx.has_t, ctx.has_bias, ctx.w_shape = t is not None, bias is not None, w.shape
+    ctx.save_for_backward(w, x, m, t, output[1])
+
+
+def _spmm_edge_heads_backward(ctx, dy, _dargmax):
+    w, x, m, t, argmax = ctx.saved_tensors
+    if dy is None:
+        return (None,) * 8
+    need = ctx.needs_input_grad
+    want = (_EH_W if need[0] else 0) | (_EH_X if need[1] else 0) | (_EH_M if need[2] else 0) | \
+           (_EH_T if (ctx.has_t and need[3]) else 0)
+    dw = dx = dm = dt = None
+    if want:
+        dw, dx, dm, dt = torch.ops.mp.spmm_edge_heads_bwd_raw(dy, w, x, m, t, argmax, ctx.graph, ctx.heads, ctx.reduce, want)
+        dw = dw.reshape(ctx.w_shape) if want & _EH_W else None
+        dx, dm, dt = (dx if want & _EH_X else None), (dm if want & _EH_M else None), (dt if want & _EH_T else None)
+    dbias = dy.sum(0) if (ctx.has_bias and need[4]) else None
+    return dw, dx, dm, dt, dbias, None, None, None
+
+
+register_autograd("mp::spmm_edge_heads", _spmm_edge_heads_backward, setup_context=_spmm_edge_heads_setup)
+
+
+def spmm_edge_heads(g, w, x, m, t=None, heads=1, reduce="sum", bias=None):
+    """y[i, slice h] = reduce_{e = (i <- j)} w[e, h] (x[j] + m[eid_e] + t[i])[slice h] + bias   (torch.ops.mp.spmm_edge_heads)
+
+    spmm_edge with one weight per entry AND head — the propagate of GeneralEdgeAttConvv1Layer / v2 (attconv.py:358-360)
+    with w = norm * alpha [nnz, H]; x [n, d] by source, m [E, d] by the entry's input position (g.eid; an inserted self
+    loop gets no m term), t [N, d] the destination's own term.  The entry values of g take no part.  2, 4 and 8 heads run
+    in one launch (mp_spmm_csr_edge_heads_f32), every other head count above one runs one launch of
+    mp_spmm_csr_edge_f32 per head on column slices.  reduce: 'sum'/'add' | 'mean' | 'max'
+    (ties: the first entry in CSR order).  float32 only; the gradient flows to w, x, m, t and bias; no float atomics
+    except in dx of 'max' (mp_spmm_heads_max_bwd_f32), which is therefore not bitwise reproducible."""
+    if reduce not in _lib.REDUCE:
+        raise ValueError(f"reduce must be one of {sorted(_lib.REDUCE)}, got {reduce!r}")
+    for name, v in (("w", w), ("x", x), ("m", m), ("t", t), ("bias", bias)):
+        if v is not None:
+            _edge_att_f32(v, name, "spmm_edge_heads")
+    if int(heads) < 1 or x.size(1) % int(heads):
+        raise ValueError(f"x has {x.size(1)} columns, not a multiple of heads = {heads}")
+    _eid_checked(g, m.size(0))
+    return torch.ops.mp.spmm_edge_heads(w, x, m, t, bias, g.handle, int(heads), _lib.REDUCE[reduce])[0]

@@ -510,6 +510,16 @@ int mp_sddmm_add_f32(const int32_t* rowptr, const int32_t* col, int64_t N, int64
  * the scores are never stored.  a_dst, a_src [N, H]. */
 int mp_gat_alpha_f32(const int32_t* rowptr, const int32_t* col, int64_t N, int64_t nnz, int32_t heads,
                      const float* a_dst, const float* a_src, float slope, float* alpha, mp_stream_t stream);
+/* the same with an edge term — the attention coefficients of the edge-feature attention layers (attconv.py:342-357),
+ * whose score <linear(cat([x_i,] x_j, ef_e))^h, att_msg^h> splits into per-node and per-edge scalars:
+ * alpha[e*H+h] = softmax over the entries e of row r of
+ *   leaky_relu(a_dst[r*H+h] + a_src[col[e]*H+h] + a_edge[eid[e]*H+h], slope),
+ * a_src [n, H], a_edge [E, H] in INPUT edge order (an entry with eid < 0 has no edge term), a_dst [N, H] or NULL (absent:
+ * msg_direction 'single').  One launch for all heads on the row loop of mp_gat_alpha_f32; the scores are never stored.
+ * N or nnz >= 2^31: MP_ERR_UNSUPPORTED. */
+int mp_edge_att_alpha_f32(const int32_t* rowptr, const int32_t* col, const int32_t* eid, int64_t N, int64_t nnz,
+                          int32_t heads, const float* a_dst, const float* a_src, const float* a_edge, float slope,
+                          float* alpha, mp_stream_t stream);
 /* softmax over each row's entries, per head: segment_softmax (sparse_adj.py:136-151),
  * torch_geometric.utils.softmax (idconv.py:327).  In-place allowed. */
 int mp_csr_row_softmax_f32(const int32_t* rowptr, int64_t N, int32_t heads,
@@ -571,6 +581,24 @@ int mp_spmm_csr_edge_f32(const int32_t* rowptr, const int32_t* col, const int32_
 int mp_spmm_edge_bwd_f32(const int32_t* rowptr, const int32_t* eid, const float* val, const int32_t* argmax, int64_t N,
                          int64_t nnz, int reduce, const float* dY, int64_t ldy, int32_t d, float* dM, int64_t ldm,
                          mp_stream_t stream);
+/* mp_spmm_csr_edge_f32 with per-head weights a [nnz, H] in the place of val — the propagate of the edge-feature attention
+ * layers (attconv.py:342-360) with a = norm * alpha:
+ *   Y[r, slice h] = reduce_{e in row r} a[e*H+h] * (X[col[e]] + M[eid[e]] + T[r])[slice h] (+ bias).
+ * Everything else as mp_spmm_csr_edge_f32: reduce MP_SUM / MP_MEAN / MP_MAX, its argmax convention, eid < 0, hub rows
+ * through pieces / finalize, no atomics, the workspace.  heads 2, 4, 8 with d % heads == 0 run in one launch (a lane's
+ * columns stay inside one head); heads == 1 is mp_spmm_csr_edge_f32 with val = a; other head counts return
+ * MP_ERR_UNSUPPORTED (run mp_spmm_csr_edge_f32 per head on column slices). */
+int mp_spmm_csr_edge_heads_f32(const int32_t* rowptr, const int32_t* col, const int32_t* eid, const float* a, int64_t N,
+                               const int32_t* plan, const int32_t* counts_host, int32_t heads, const float* X,
+                               int64_t ldx, const float* M, int64_t ldm, const float* T, int64_t ldt, float* Y,
+                               int64_t ldy, int32_t d, int reduce, const float* bias, int32_t* argmax, void* ws,
+                               size_t ws_bytes, mp_stream_t stream);
+/* backward of mp_spmm_csr_edge_heads_f32 into M, dM [E, d] ZEROED by the caller: mp_spmm_edge_bwd_f32 with the weight of
+ * column c's head, dM[eid[e], c] = a[e*H + c/(d/H)] (/ entry count of the row for MP_MEAN) * dY[row of e, c]; MP_MAX
+ * writes only where e == argmax[r, c].  Any heads >= 1 with d % heads == 0.  Plain stores, the same bits every run. */
+int mp_spmm_edge_heads_bwd_f32(const int32_t* rowptr, const int32_t* eid, const float* a, int32_t heads,
+                               const int32_t* argmax, int64_t N, int64_t nnz, int reduce, const float* dY, int64_t ldy,
+                               int32_t d, float* dM, int64_t ldm, mp_stream_t stream);
 /* backward of the multi-head weighted max into V: dV[col[e], c] += a[e*H + c/(d/H)] * dY[r, c] for e = argmax[r, c]
  * >= 0 (attconv.py:93-104, :196-205 with aggr 'max').  One launch for all heads; no-return float atomics, so dV
  * (zeroed by the caller) is not bitwise reproducible.  N >= 2^31: MP_ERR_UNSUPPORTED. */
