@@ -35,6 +35,18 @@ def make_dataset(n_graphs=100, n=64, m=2, seed=0, label_dims=10):
     return graphs, labels, len(bins)
 
 
+def device_labels(graphs, dev, label_dims=10):
+    """the same labels from graphgym_amd.structure: the coefficients from the triangle kernel on the union of the
+    graphs, binned over the whole dataset on the device (no networkx call per node)"""
+    from graphgym_amd import structure
+    ei, _, n = union(graphs, [np.zeros(G.number_of_nodes(), dtype=np.int64) for G in graphs], dev)
+    sizes = [0] + [G.number_of_nodes() for G in graphs]
+    tensors, _, n_cls = structure.augment(ga.CSRGraph.from_edge_index(ei, n), torch.tensor(np.cumsum(sizes)), [], [],
+                                          label="node_clustering_coefficient", label_dim=label_dims)
+    y = tensors["node_clustering_coefficient_label"].cpu().numpy()
+    return [part for part in np.split(y, np.cumsum(sizes)[1:-1])], n_cls
+
+
 def union(graphs, labels, dev):
     """one batch = disjoint union of graphs (loader.py:247-251)"""
     parts, off = [], 0
@@ -47,8 +59,10 @@ def union(graphs, labels, dev):
     return ei, y, off
 
 
-def run(kind, epochs, dev, seed=0, radius=3, d=128, hipgraph=False):
+def run(kind, epochs, dev, seed=0, radius=3, d=128, hipgraph=False, labels_from="host"):
     graphs, labels, n_cls = make_dataset(seed=0)
+    if labels_from == "device":
+        labels, n_cls = device_labels(graphs, dev)
     torch.manual_seed(seed)
     split = int(0.8 * len(graphs))
     sets = {}
@@ -98,6 +112,8 @@ if __name__ == "__main__":
     ap.add_argument("--epochs", type=int, default=300)
     ap.add_argument("--hipgraph", action="store_true", help="capture the training step into a HIP graph")
     ap.add_argument("--seeds", type=int, default=1, help="runs per model (weight initialisation seeds 0..seeds-1)")
+    ap.add_argument("--labels", choices=("host", "device"), default="host",
+                    help="host: nx.clustering per node; device: graphgym_amd.structure.augment")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     # the reference's ScaleFree column (README.md:104-118; TF path, RTX 2080 Ti, 1000 epochs, its own dataset and class
@@ -107,7 +123,7 @@ if __name__ == "__main__":
     for kind in ("gcn", "idgcn", "sage", "idsage", "gat", "idgat", "gin", "idgin"):
         accs = []
         for seed in range(args.seeds):
-            r = run(kind, args.epochs, dev, seed=seed, hipgraph=args.hipgraph)
+            r = run(kind, args.epochs, dev, seed=seed, hipgraph=args.hipgraph, labels_from=args.labels)
             r["seed"] = seed
             accs.append(r["best_val_acc"])
             print(json.dumps(r), flush=True)

@@ -311,7 +311,8 @@ head_dict = {'node': GNNNodeHead, 'graph': GNNGraphHead,      # head.py:122-127
 class GNN(nn.Module):
     """graphgym/models/gnn.py:123-168 with stage_type 'stack' (the skip stages concatenate / add around the same
     layers and are not on the path the BASELINE configs drive).  The feature-augmentation `preprocess` module of the
-    reference holds no parameters and is outside the path (SURVEY.md §2 #11): inputs arrive already assembled."""
+    reference holds no parameters and is outside the path: inputs arrive already assembled (the structural features and labels it
+    concatenates: graphgym_amd.structure.augment)."""
 
     def __init__(self, dim_in, dim_out, **kwargs):
         super().__init__()

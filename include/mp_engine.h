@@ -704,6 +704,30 @@ int mp_hop_distances(const int32_t* rowptr, const int32_t* col, int64_t N, int64
                      int64_t n_pairs, int32_t* dist, mp_stream_t stream);
 
 /* ------------------------------------------------------------------ *
+ * Structural labels and features (graphgym/models/feature_augment.py)  *
+ * The engine's CSR, columns ascending inside a row.  Integer results:  *
+ * bit-reproducible.  Nothing is allocated, no synchronisation.         *
+ * ------------------------------------------------------------------ */
+/* The integers of nx.clustering (clustering_coefficient_fun, feature_augment.py:81-82; nx.average_clustering of
+ * graph_clustering_fun, :105-107) for a SYMMETRIC operator that stores no (r, c) twice: deg[u] = the entries of row u
+ * with col != u, tri2[u] = the sum over the stored entries (u, v), v != u, of |{w in row u and row v : w != u, w != v}|
+ * = twice the triangles through u, the t that networkx divides by d (d - 1).  Explicit self loops are skipped, as
+ * networkx skips them.  tri2 is zeroed by the call (an async memset on the stream).  row_of from mp_csr_row_ids: the
+ * work is shared by stored entry, so a hub row is spread over many waves.  N = 0 or nnz = 0: MP_OK without a launch. */
+int mp_csr_triangles(const int32_t* rowptr, const int32_t* col, const int32_t* row_of, int64_t N, int64_t nnz,
+                     int64_t* tri2, int32_t* deg, mp_stream_t stream);
+/* The integers of path_len_fun (feature_augment.py:60-63: the mean of nx.shortest_path_length(G, source=x) over the
+ * nodes x reaches, itself included) and of nx.average_shortest_path_length (graph_path_len_fun, :101-103): for source
+ * sources[s] (global id) inside its graph source_graph[s] of graph_ptr [n_graphs + 1], dist_sum[s] = the sum of the hop
+ * distances to every node it reaches and reached[s] = their number, the source (distance 0) included.  The search of
+ * mp_hop_distances, one workgroup per source, bitmaps in LDS: max_graph_nodes (largest graph that holds a source) above
+ * 65536 is MP_ERR_UNSUPPORTED. */
+int mp_hop_sums(const int32_t* rowptr, const int32_t* col, int64_t N, int64_t nnz,
+                const int64_t* graph_ptr, int64_t n_graphs, int64_t max_graph_nodes,
+                const int64_t* sources, const int32_t* source_graph, int64_t n_sources,
+                int64_t* dist_sum, int32_t* reached, mp_stream_t stream);
+
+/* ------------------------------------------------------------------ *
  * Host-side sharding of independent units over ranks (not a device op) *
  * graphgym/loader.py:247-251 (a batch is a disjoint union of graphs),  *
  * graphgym/models/transform.py:24-36 (ego nets are disjoint): units by  *
