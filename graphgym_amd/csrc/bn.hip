@@ -5,10 +5,12 @@
 // Why it is here: at the headline size ([10^7, 256] activations) torch's batch_norm_backward_reduce_kernel
 // runs one workgroup per feature column and takes 0.52 s per call — 74 % of a GIN training step
 // (profiles/r01_gin_step_library_bn.txt).  These are plain HBM-bound passes:
-//   forward   stats  : one read of x            -> per-column sum / sum of squares (shifted by a pivot row)
+//   forward   stats  : one read of x            -> per-column sum / sum of squares (shifted by the median of three rows)
 //             apply  : read x, write y          -> y = act(x * scale + shift)
 //   backward  stats  : read dy (, y), x         -> sum(g), sum(g * x)  with g = dy * [y > 0]
 //             apply  : read dy (, y), x, write  -> dx = A * g + B * x + C   (per-column constants)
+//   skip block  apply  : read x, skip, write out  -> out = act(skip + BN(x)) or [act(skip) | act(BN(x))]  (gnn.py:49-60)
+//               bwd    : the statistics pass writes g (= d skip), the apply pass reads it: 7 instead of 8 N d
 // Column sums are accumulated per workgroup over a contiguous run of rows (fp32, <= a few thousand terms
 // per lane), written as partial slabs and combined in double precision in slab order: deterministic and
 // accurate at 10^7 rows.
@@ -38,12 +40,29 @@ __host__ __device__ inline BnGeom bn_geom(int d) {
   return g;
 }
 
-// MODE 0: a = sum(x - pivot), b = sum((x - pivot)^2)          (forward statistics)
+// MODE 0: a = sum(x - pivot), b = sum((x - pivot)^2)          (forward statistics; pivot = bn_pivot(x))
 // MODE 1: a = sum(g),         b = sum(g * (x - pivot)),  g = dy * [y > 0] when y != nullptr, pivot = mean
+// MODE 2: MODE 1 with y given, and g written to gout on the way: the skip block's d(skip), which its apply pass then
+//         reads in place of dy and y
 // the affine scale of the apply pass, from the ROUNDED invstd the forward hands out: the forward and a backward that
 // recomputes the activation from x get the same bits
 __host__ __device__ __forceinline__ float bn_scale(float gamma, float invstd) {
   return (float)((double)gamma * (double)invstd);
+}
+
+// The pivot of the forward statistics: per column the median of rows 0, N / 2 and N - 1.  The sums are taken of
+// x - pivot, and var = E[v^2] - E[v]^2 loses (pivot - mean)^2 / var of the fp32 partials' precision: a single sample is an
+// outlier too often — row 0 of a preferential-attachment graph is its largest hub, ten and more standard deviations
+// from the column mean behind an unnormalised add aggregation.  The median of three is exact to select, so the
+// statistics kernel and the finalize kernel get the same bits.
+template <int W>
+__device__ __forceinline__ void bn_pivot(const float* __restrict__ x, int64_t ldx, int64_t N, int c0, float (&pv)[W]) {
+  float a[W], b[W], c[W];
+  load_vec<W>(x + c0, a);
+  load_vec<W>(x + (N / 2) * ldx + c0, b);
+  load_vec<W>(x + (N - 1) * ldx + c0, c);
+#pragma unroll
+  for (int k = 0; k < W; ++k) pv[k] = fmaxf(fminf(a[k], b[k]), fminf(fmaxf(a[k], b[k]), c[k]));
 }
 
 template <int W, int MODE>
@@ -54,7 +73,8 @@ __global__ __launch_bounds__(kBlock) void bn_colsum_kernel(const float* __restri
                                                            int64_t rows_per_block, float* __restrict__ partial,
                                                            const float* __restrict__ mx_gamma = nullptr,
                                                            const float* __restrict__ mx_beta = nullptr,
-                                                           const float* __restrict__ mx_invstd = nullptr) {
+                                                           const float* __restrict__ mx_invstd = nullptr,
+                                                           float* __restrict__ gout = nullptr, int64_t ldg = 0) {
   // mx_invstd != NULL (MODE 1): the ReLU mask [y > 0] is recomputed from x — y = relu(fmaf(x - mean, scale, beta))
   // with scale = float(gamma * invstd), the forward's own expression on the forward's own operands, bit for bit —
   // instead of reading y
@@ -70,11 +90,14 @@ __global__ __launch_bounds__(kBlock) void bn_colsum_kernel(const float* __restri
     float a[W], b[W], pv[W];
 #pragma unroll
     for (int k = 0; k < W; ++k) { a[k] = 0.f; b[k] = 0.f; pv[k] = 0.f; }
-    if (on) load_vec<W>(pivot + c0, pv);
+    if (on) {
+      if (MODE == 0) bn_pivot<W>(x, ldx, N, c0, pv);      // `pivot` is not read
+      else load_vec<W>(pivot + c0, pv);
+    }
     float sc[W], bt[W];
 #pragma unroll
     for (int k = 0; k < W; ++k) { sc[k] = 0.f; bt[k] = 0.f; }
-    if (MODE == 1 && mx_invstd != nullptr && on) {
+    if (MODE != 0 && mx_invstd != nullptr && on) {
 #pragma unroll
       for (int k = 0; k < W; ++k)
         if (c0 + k < d) {
@@ -105,6 +128,7 @@ __global__ __launch_bounds__(kBlock) void bn_colsum_kernel(const float* __restri
 #pragma unroll
             for (int k = 0; k < W; ++k) gv[k] = yv[k] > 0.f ? gv[k] : 0.f;
           }
+          if (MODE == 2) store_vec<W>(gout + r * ldg + c0, gv);
 #pragma unroll
           for (int k = 0; k < W; ++k) {
             a[k] += gv[k];
@@ -168,7 +192,7 @@ __device__ __forceinline__ bool bn_col_sums(const float* __restrict__ partial, i
 
 // forward finalize: mean, invstd, unbiased variance, and the affine of the apply pass
 __global__ __launch_bounds__(kBlock) void bn_fwd_finalize_kernel(const float* __restrict__ partial, int nblk,
-                                                                 const float* __restrict__ pivot, int64_t N,
+                                                                 const float* __restrict__ x, int64_t ldx, int64_t N,
                                                                  int32_t d, const float* __restrict__ gamma,
                                                                  const float* __restrict__ beta, float eps,
                                                                  float* mean, float* invstd, float* var_unbiased,
@@ -179,7 +203,9 @@ __global__ __launch_bounds__(kBlock) void bn_fwd_finalize_kernel(const float* __
   const double m_shift = s1 / (double)N;
   double var = s2 / (double)N - m_shift * m_shift;      // biased (training normalisation)
   if (var < 0.0) var = 0.0;
-  const double m = (double)pivot[c] + m_shift;
+  float pv[1];
+  bn_pivot<1>(x, ldx, N, c, pv);
+  const double m = (double)pv[0] + m_shift;
   const double istd = 1.0 / sqrt(var + (double)eps);
   mean[c] = (float)m;
   invstd[c] = (float)istd;
@@ -269,6 +295,58 @@ __global__ __launch_bounds__(kBlock) void bn_apply_kernel(const float* __restric
   }
 }
 
+// The skip block's apply pass (graphgym/models/gnn.py:49-60 behind a last layer without activation), one launch:
+//   SUM    (CONCAT = false, d_skip == d): out = act(skip + ((x - ctr) * p0 + p1))
+//   CONCAT                              : out[:, :d_skip] = act(skip), out[:, d_skip:] = act((x - ctr) * p0 + p1)
+// The BN term is bn_apply_kernel<W, 0>'s own fmaf.  WS / WX: vector widths of the skip slab and of the BN slab (equal in
+// SUM); a row is d_skip / WS + d / WX work items.
+template <int WS, int WX, bool CONCAT>
+__global__ __launch_bounds__(kBlock) void bn_apply_skip_kernel(const float* __restrict__ x, int64_t ldx,
+                                                               const float* __restrict__ skip, int64_t ldskip,
+                                                               const float* __restrict__ p0,
+                                                               const float* __restrict__ p1,
+                                                               const float* __restrict__ ctr, int relu, int64_t N,
+                                                               int32_t d, int32_t d_skip, float* __restrict__ out,
+                                                               int64_t ldo) {
+  const int gs = CONCAT ? (d_skip + WS - 1) / WS : 0;
+  const int groups = gs + (d + WX - 1) / WX;
+  const int64_t total = N * groups;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / groups;
+    const int j = (int)(i - r * groups);
+    if (CONCAT && j < gs) {
+      const int c0 = j * WS;
+      float sv[WS];
+      load_vec<WS>(skip + r * ldskip + c0, sv);
+      if (relu) {
+#pragma unroll
+        for (int k = 0; k < WS; ++k) sv[k] = fmaxf(sv[k], 0.f);
+      }
+      store_vec<WS>(out + r * ldo + c0, sv);
+    } else {
+      const int c0 = (j - gs) * WX;
+      float xv[WX], a[WX], b[WX], o[WX], mv[WX];
+      load_vec<WX>(x + r * ldx + c0, xv);
+      load_vec<WX>(p0 + c0, a);
+      load_vec<WX>(p1 + c0, b);
+      load_vec<WX>(ctr + c0, mv);
+#pragma unroll
+      for (int k = 0; k < WX; ++k) o[k] = fmaf(xv[k] - mv[k], a[k], b[k]);
+      if (!CONCAT) {
+        float sv[WX];
+        load_vec<WX>(skip + r * ldskip + c0, sv);
+#pragma unroll
+        for (int k = 0; k < WX; ++k) o[k] = sv[k] + o[k];
+      }
+      if (relu) {
+#pragma unroll
+        for (int k = 0; k < WX; ++k) o[k] = fmaxf(o[k], 0.f);
+      }
+      store_vec<WX>(out + r * ldo + (CONCAT ? d_skip : 0) + c0, o);
+    }
+  }
+}
+
 static int bn_blocks(int64_t N) {
   int64_t b = ceil_div(N, 64);
   if (b < 1) b = 1;
@@ -302,6 +380,26 @@ int mp_bn_ws_bytes(int64_t N, int32_t d, size_t* bytes_host) {
   return MP_OK;
 }
 
+// the statistics and finalize launches of the forward: mean / invstd / var_unbiased, and the affine of the apply pass in
+// L.v[0] (scale) and L.v[1] (shift)
+static int bn_fwd_stats(const float* x, int64_t ldx, int64_t N, int32_t d, const float* gamma, const float* beta,
+                        float eps, float* mean, float* invstd, float* var_unbiased, const BnWs& L, bool vec,
+                        hipStream_t st) {
+  const int nblk = bn_blocks(N);
+  const int64_t rpb = ceil_div(N, nblk);
+  if (vec)       // the sums are shifted by bn_pivot(x), which both kernels take from x themselves
+    hipLaunchKernelGGL((bn_colsum_kernel<4, 0>), dim3(nblk), dim3(kBlock), 0, st, x, ldx, nullptr, 0, nullptr, 0, nullptr,
+                       N, d, rpb, L.partial);
+  else
+    hipLaunchKernelGGL((bn_colsum_kernel<1, 0>), dim3(nblk), dim3(kBlock), 0, st, x, ldx, nullptr, 0, nullptr, 0, nullptr,
+                       N, d, rpb, L.partial);
+  MP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(bn_fwd_finalize_kernel, dim3((unsigned)ceil_div(d, 16)), dim3(kBlock), 0, st, L.partial, nblk,
+                     x, ldx, N, d, gamma, beta, eps, mean, invstd, var_unbiased, L.v[0], L.v[1]);
+  MP_LAUNCH_CHECK();
+  return MP_OK;
+}
+
 int mp_bn_train_fwd_f32(const float* x, int64_t ldx, int64_t N, int32_t d, const float* gamma, const float* beta,
                         float eps, int relu, float* y, int64_t ldy, float* mean, float* invstd,
                         float* var_unbiased, void* ws, size_t ws_bytes, mp_stream_t stream) {
@@ -310,20 +408,9 @@ int mp_bn_train_fwd_f32(const float* x, int64_t ldx, int64_t N, int32_t d, const
   bn_ws_layout(N, d, ws, &L);
   if (!ws || ws_bytes < L.total) return MP_ERR_WORKSPACE;
   hipStream_t st = as_stream(stream);
-  const int nblk = bn_blocks(N);
-  const int64_t rpb = ceil_div(N, nblk);
   const bool vec = d % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && bn_al(x, 16) && bn_al(y, 16);
-  const float* pivot = x;     // row 0: any sample of the column keeps the shifted sums well conditioned
-  if (vec)
-    hipLaunchKernelGGL((bn_colsum_kernel<4, 0>), dim3(nblk), dim3(kBlock), 0, st, x, ldx, nullptr, 0, nullptr, 0, pivot,
-                       N, d, rpb, L.partial);
-  else
-    hipLaunchKernelGGL((bn_colsum_kernel<1, 0>), dim3(nblk), dim3(kBlock), 0, st, x, ldx, nullptr, 0, nullptr, 0, pivot,
-                       N, d, rpb, L.partial);
-  MP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(bn_fwd_finalize_kernel, dim3((unsigned)ceil_div(d, 16)), dim3(kBlock), 0, st, L.partial, nblk,
-                     pivot, N, d, gamma, beta, eps, mean, invstd, var_unbiased, L.v[0], L.v[1]);
-  MP_LAUNCH_CHECK();
+  const int rc = bn_fwd_stats(x, ldx, N, d, gamma, beta, eps, mean, invstd, var_unbiased, L, vec, st);
+  if (rc != MP_OK) return rc;
   if (vec)
     hipLaunchKernelGGL((bn_apply_kernel<4, 0>), dim3(flat_grid(N * (d / 4))), dim3(kBlock), 0, st, x, ldx, nullptr, 0,
                        nullptr, 0, L.v[0], L.v[1], nullptr, mean, relu, N, d, y, ldy);
@@ -334,11 +421,55 @@ int mp_bn_train_fwd_f32(const float* x, int64_t ldx, int64_t N, int32_t d, const
   return MP_OK;
 }
 
+int mp_bn_train_fwd_skip_f32(const float* x, int64_t ldx, const float* skip, int64_t ldskip, int64_t N, int32_t d,
+                             int32_t d_skip, int mode, const float* gamma, const float* beta, float eps, int relu,
+                             float* out, int64_t ldo, float* mean, float* invstd, float* var_unbiased, void* ws,
+                             size_t ws_bytes, mp_stream_t stream) {
+  if (N <= 0 || d <= 0 || d_skip <= 0 || !x || !skip || !out || !mean || !invstd || !var_unbiased || ldx < d ||
+      ldskip < d_skip)
+    return MP_ERR_INVALID_ARG;
+  if (mode != MP_BN_SKIP_SUM && mode != MP_BN_SKIP_CONCAT) return MP_ERR_INVALID_ARG;
+  if (mode == MP_BN_SKIP_SUM && d_skip != d) return MP_ERR_INVALID_ARG;
+  const bool cat = mode == MP_BN_SKIP_CONCAT;
+  if (ldo < (cat ? (int64_t)d_skip + d : (int64_t)d)) return MP_ERR_INVALID_ARG;
+  BnWs L;
+  bn_ws_layout(N, d, ws, &L);
+  if (!ws || ws_bytes < L.total) return MP_ERR_WORKSPACE;
+  hipStream_t st = as_stream(stream);
+  // a launch takes its vector form when every pointer it forms is 16-byte aligned: the statistics read x alone; the
+  // apply pass writes the BN slab at out (SUM) or out + d_skip (CONCAT) and the skip slab at out
+  const bool vx = d % 4 == 0 && ldx % 4 == 0 && bn_al(x, 16);
+  const bool vo = ldo % 4 == 0 && bn_al(out, 16);
+  const bool vs = d_skip % 4 == 0 && ldskip % 4 == 0 && bn_al(skip, 16) && vo;
+  const int rc = bn_fwd_stats(x, ldx, N, d, gamma, beta, eps, mean, invstd, var_unbiased, L, vx, st);
+  if (rc != MP_OK) return rc;
+#define MP_BN_SKIP_LAUNCH(WS, WX, CAT)                                                                              \
+  hipLaunchKernelGGL((bn_apply_skip_kernel<WS, WX, CAT>),                                                           \
+                     dim3(flat_grid(N * ((CAT ? (int64_t)d_skip / WS : 0) + (int64_t)d / WX))), dim3(kBlock), 0, st, \
+                     x, ldx, skip, ldskip, L.v[0], L.v[1], mean, relu, N, d, d_skip, out, ldo)
+  if (!cat) {
+    if (vx && vs) MP_BN_SKIP_LAUNCH(4, 4, false);
+    else MP_BN_SKIP_LAUNCH(1, 1, false);
+  } else {
+    const bool vr = vx && vo && d_skip % 4 == 0;      // the right slab starts at out + d_skip
+    if (vs && vr) MP_BN_SKIP_LAUNCH(4, 4, true);
+    else if (vs) MP_BN_SKIP_LAUNCH(4, 1, true);
+    else if (vr) MP_BN_SKIP_LAUNCH(1, 4, true);
+    else MP_BN_SKIP_LAUNCH(1, 1, true);
+  }
+#undef MP_BN_SKIP_LAUNCH
+  MP_LAUNCH_CHECK();
+  return MP_OK;
+}
+
 static int bn_bwd_common(const float* dy, int64_t lddy, const float* y, int64_t ldy, const float* x, int64_t ldx,
                          int64_t N, int32_t d, const float* gamma, const float* beta, int mask_from_x,
                          const float* mean, const float* invstd, float* dx, int64_t lddx, float* dgamma, float* dbeta,
-                         void* ws, size_t ws_bytes, hipStream_t st) {
-  if (N <= 0 || d <= 0 || !dy || !x || !mean || !invstd || !dx || lddy < d || ldx < d || lddx < d || (y && ldy < d))
+                         void* ws, size_t ws_bytes, hipStream_t st, float* dskip = nullptr, int64_t lddskip = 0) {
+  // dskip != NULL (with y): the statistics pass also writes g = dy * [y > 0] there and the apply pass reads it in
+  // place of dy and y — same terms, same order, one [N, d] read fewer than masking dy twice and writing g apart
+  if (N <= 0 || d <= 0 || !dy || !x || !mean || !invstd || !dx || lddy < d || ldx < d || lddx < d || (y && ldy < d) ||
+      (dskip && (!y || mask_from_x || lddskip < d)))
     return MP_ERR_INVALID_ARG;
   BnWs L;
   bn_ws_layout(N, d, ws, &L);
@@ -346,11 +477,18 @@ static int bn_bwd_common(const float* dy, int64_t lddy, const float* y, int64_t 
   const int nblk = bn_blocks(N);
   const int64_t rpb = ceil_div(N, nblk);
   const bool vec = d % 4 == 0 && ldx % 4 == 0 && lddy % 4 == 0 && lddx % 4 == 0 && (!y || ldy % 4 == 0) &&
-                   bn_al(x, 16) && bn_al(dy, 16) && bn_al(y, 16) && bn_al(dx, 16) && (!mask_from_x || bn_al(beta, 16));
+                   bn_al(x, 16) && bn_al(dy, 16) && bn_al(y, 16) && bn_al(dx, 16) && (!mask_from_x || bn_al(beta, 16)) &&
+                   lddskip % 4 == 0 && bn_al(dskip, 16);
   const float* mg = mask_from_x ? gamma : nullptr;
   const float* mb = mask_from_x ? beta : nullptr;
   const float* mi = mask_from_x ? invstd : nullptr;
-  if (vec)
+  if (dskip && vec)
+    hipLaunchKernelGGL((bn_colsum_kernel<4, 2>), dim3(nblk), dim3(kBlock), 0, st, x, ldx, dy, lddy, y, ldy, mean, N,
+                       d, rpb, L.partial, nullptr, nullptr, nullptr, dskip, lddskip);
+  else if (dskip)
+    hipLaunchKernelGGL((bn_colsum_kernel<1, 2>), dim3(nblk), dim3(kBlock), 0, st, x, ldx, dy, lddy, y, ldy, mean, N,
+                       d, rpb, L.partial, nullptr, nullptr, nullptr, dskip, lddskip);
+  else if (vec)
     hipLaunchKernelGGL((bn_colsum_kernel<4, 1>), dim3(nblk), dim3(kBlock), 0, st, x, ldx, dy, lddy, y, ldy, mean, N,
                        d, rpb, L.partial, mg, mb, mi);
   else
@@ -361,6 +499,7 @@ static int bn_bwd_common(const float* dy, int64_t lddy, const float* y, int64_t 
                      N, d, gamma, mean, invstd, dgamma, dbeta, L.v[0], L.v[1], L.v[2], mask_from_x ? L.v[3] : nullptr);
   MP_LAUNCH_CHECK();
   const float* msc = mask_from_x ? L.v[3] : nullptr;
+  if (dskip) { dy = dskip; lddy = lddskip; y = nullptr; }     // g is on hand: the mask is already applied
   if (vec)
     hipLaunchKernelGGL((bn_apply_kernel<4, 1>), dim3(flat_grid(N * (d / 4))), dim3(kBlock), 0, st, x, ldx, dy, lddy, y,
                        ldy, L.v[0], L.v[1], L.v[2], mean, 0, N, d, dx, lddx, msc, mb);
@@ -385,6 +524,16 @@ int mp_bn_train_bwd_relu_f32(const float* dy, int64_t lddy, const float* x, int6
                              mp_stream_t stream) {
   return bn_bwd_common(dy, lddy, nullptr, 0, x, ldx, N, d, gamma, beta, 1, mean, invstd, dx, lddx, dgamma, dbeta, ws,
                        ws_bytes, as_stream(stream));
+}
+
+int mp_bn_train_bwd_skip_f32(const float* dy, int64_t lddy, const float* out, int64_t ldo, const float* x, int64_t ldx,
+                             int64_t N, int32_t d, const float* gamma, const float* mean, const float* invstd,
+                             float* dx, int64_t lddx, float* dskip, int64_t lddskip, float* dgamma, float* dbeta,
+                             void* ws, size_t ws_bytes, mp_stream_t stream) {
+  if (out && !dskip) return MP_ERR_INVALID_ARG;
+  // out NULL = no activation: d(skip) is dy itself and nothing is written for it
+  return bn_bwd_common(dy, lddy, out, ldo, x, ldx, N, d, gamma, nullptr, 0, mean, invstd, dx, lddx, dgamma, dbeta, ws,
+                       ws_bytes, as_stream(stream), out ? dskip : nullptr, out ? lddskip : 0);
 }
 
 }  // extern "C"

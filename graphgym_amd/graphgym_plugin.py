@@ -182,6 +182,33 @@ def _folded_forward(self, batch):
     return batch
 
 
+def _stage_type():
+    """cfg.gnn.stage_type as the reference's block reads it at call time: GraphGym's own cfg when it is loaded"""
+    import sys
+    mod = sys.modules.get("graphgym.config")
+    c = getattr(mod, "cfg", None)
+    if c is None:
+        from .config import cfg as c
+    return getattr(c.gnn, "stage_type", None)
+
+
+def _skip_block_forward(self, batch):
+    """GNNSkipBlock.forward (gnn.py:49-60) with the last layer's BatchNorm, the skip add / concatenation and the ReLU as
+    one engine pass (harness.skip_block_forward); whatever does not meet its conditions runs the original forward"""
+    from .harness import skip_block_forward
+    stage_type = _stage_type()
+    if stage_type not in ("skipsum", "skipconcat"):
+        return self._mp_orig_block_forward(batch)
+    return skip_block_forward(self, batch, stage_type, orig=self._mp_orig_block_forward)
+
+
+def _is_skip_block(mod):
+    import torch.nn as nn
+    f = getattr(mod, "f", None)
+    return (isinstance(f, nn.Sequential) and len(f) > 0 and hasattr(mod, "act")
+            and all(hasattr(m, "layer") and isinstance(getattr(m, "post_layer", None), nn.Sequential) for m in f))
+
+
 def accelerate(model, fold_eval=True):
     """Put the post-ops of a BUILT GraphGym model on the engine.  Walks the model for GraphGym's layer wrapper
     (GeneralLayer: `.layer`, `.post_layer`, `.has_l2norm`; graphgym/models/layer.py:16-47) and
@@ -189,10 +216,15 @@ def accelerate(model, fold_eval=True):
       * swaps post_layer's nn.BatchNorm1d (+ the ReLU behind it) for graphgym_amd.nn.BatchNorm1d(relu=...) — training
         mode then runs the statistics, normalisation, ReLU and the whole backward as HBM-bound engine passes instead
         of torch's kernels (its batch_norm_backward_reduce takes 0.5 s per call on a [10^7, 256] activation);
+      * patches the forward of every skip block (GNNSkipBlock: `.f`, a Sequential of layer wrappers, and `.act`;
+        graphgym/models/gnn.py:30-60) once: in training mode the last layer's BatchNorm, the block's `x + f(x)` /
+        `cat(x, f(x))` and its ReLU become one engine pass (graphgym_amd.nn.bn_skip_act), cfg.gnn.stage_type read at
+        call time as the reference does; a block with dropout, without BatchNorm, with another activation (a shared
+        nn.PReLU included) or in eval mode runs its original forward;
       * in eval mode (under no_grad) folds conv bias + BatchNorm affine + ReLU + the row L2-normalisation into the
         aggregation's row flush for the GCN-type layers (gcnconv, gcnidconv).
 
-    Returns the number of wrappers touched.  Call it once after create_model(); state_dict keys, parameter objects
+    Returns the number of wrappers touched (skip blocks are not counted).  Call it once after create_model(); state_dict keys, parameter objects
     and numerics (to fp32 rounding) are unchanged."""
     import types
     import torch.nn as nn
@@ -206,4 +238,8 @@ def accelerate(model, fold_eval=True):
             mod._mp_orig_forward = mod.forward
             mod.forward = types.MethodType(_folded_forward, mod)
         touched += 1 if (n or fold_eval) else 0
+    for mod in model.modules():
+        if _is_skip_block(mod) and not hasattr(mod, "_mp_orig_block_forward"):
+            mod._mp_orig_block_forward = mod.forward
+            mod.forward = types.MethodType(_skip_block_forward, mod)
     return touched

@@ -4,9 +4,10 @@ model shapes of the reference's two entry points and its training step order.
     TfgNodeModel   the eight keras models of main_zd.py:28-243 (n conv layers -> Flatten ->
                    Dense(256, relu) -> Dense(num_labels)); GCN / GAT families hard-code 3 layers
                    (main_zd.py:33-35,82-84), SAGE / GIN use cfg.gnn.layers_mp (:131-132,178-187)
-    GNN            graphgym/models/gnn.py:123-168 with stage 'stack', module for module (the reference's own
-                   state dicts load with strict=True): pre_mp.Layer_i -> mp.layer{i} (GeneralLayer: conv -> BN ->
-                   dropout -> act, layer.py:16-47) -> row L2-normalise (gnn.py:79-80) -> post_mp.layer_post_mp
+    GNN            graphgym/models/gnn.py:123-168, module for module (the reference's own state dicts load with
+                   strict=True): pre_mp.Layer_i -> mp.layer{i} (stage 'stack'; GeneralLayer: conv -> BN -> dropout ->
+                   act, layer.py:16-47) or mp.block{i}.f.{j} (stages 'skipsum' / 'skipconcat', gnn.py:30-60, 84-109)
+                   -> row L2-normalise (gnn.py:79-80, 107-108) -> post_mp.layer_post_mp
                    (node head + label gather head.py:19-37, or graph head with ego add-pool head.py:96-119)
     train_step     zero_grad -> forward -> loss -> backward -> [gradient all-reduce] -> step
                    (graphgym/train.py:18-25, 47-56)
@@ -234,6 +235,86 @@ class GNNStackStage(nn.Module):
         return batch
 
 
+def _act_module():
+    return nn.ReLU() if cfg.gnn.act == "relu" else getattr(nn, cfg.gnn.act)()
+
+
+def skip_block_forward(block, batch, stage_type, orig=None):
+    """GNNSkipBlock.forward (gnn.py:49-60) for a block `f` of layer wrappers (`.layer`, `.post_layer`, `.has_l2norm`) and
+    an activation `act`.  When the last layer's post-ops are exactly one BatchNorm1d in training mode (no dropout, no
+    fused ReLU of its own) and the block's activation is ReLU, the BatchNorm, the skip add / concatenation and the
+    activation are ONE graphgym_amd.nn.bn_skip_act call behind the last conv; anything else is the reference's
+    composition (`orig(batch)` when given: the forward graphgym_plugin.accelerate() replaced)."""
+    if stage_type not in ("skipsum", "skipconcat"):
+        raise ValueError("cfg.gnn.stage_type must in [skipsum, skipconcat]")
+    last = block.f[-1]
+    post = list(last.post_layer)
+    fused = (len(post) == 1 and isinstance(post[0], nn.BatchNorm1d) and not getattr(post[0], "relu", False)
+             and (post[0].training or not post[0].track_running_stats) and type(block.act) is nn.ReLU and not last.has_l2norm
+             and isinstance(batch.node_feature, torch.Tensor) and batch.node_feature.is_cuda)
+    if not fused and orig is not None:
+        return orig(batch)
+    x = batch.node_feature
+    if not fused:
+        h = block.f(batch).node_feature
+        batch.node_feature = block.act(x + h if stage_type == "skipsum" else torch.cat((x, h), 1))
+        return batch
+    for layer in list(block.f)[:-1]:
+        batch = layer(batch)
+    batch = last.layer(batch)
+    batch.node_feature = mpnn.bn_skip_act(post[0], batch.node_feature, x, stage_type, relu=True)
+    return batch
+
+
+class GNNSkipBlock(nn.Module):
+    """graphgym/models/gnn.py:30-60: `f` = Sequential of GNNLayers, the last without activation; forward =
+    act(x + f(x)) (skipsum) or act(cat(x, f(x))) (skipconcat), with the last BatchNorm, the skip operand and the
+    activation in one engine pass where skip_block_forward's conditions hold.  `self.f(batch)` alone stays the plain,
+    unfused layers."""
+
+    def __init__(self, dim_in, dim_out, num_layers):
+        super().__init__()
+        layers = []
+        for i in range(num_layers - 1):
+            layers.append(GNNLayer(dim_in if i == 0 else dim_out, dim_out))
+        layers.append(GNNLayer(dim_in if num_layers == 1 else dim_out, dim_out, has_act=False))
+        self.f = nn.Sequential(*layers)
+        self.act = _act_module()
+        if cfg.gnn.stage_type == 'skipsum':
+            assert dim_in == dim_out, 'Sum skip must have same dim_in, dim_out'
+
+    def forward(self, batch):
+        return skip_block_forward(self, batch, cfg.gnn.stage_type)
+
+
+class GNNSkipStage(nn.Module):
+    """graphgym/models/gnn.py:84-109: children named block{i}, each cfg.gnn.skip_every layers; skipconcat widens the
+    input of block i to dim_in + i * dim_out; row L2-normalisation behind the last one"""
+
+    def __init__(self, dim_in, dim_out, num_layers):
+        super().__init__()
+        assert num_layers % cfg.gnn.skip_every == 0, \
+            'cfg.gnn.skip_every must be multiples of cfg.gnn.layer_mp(excluding head layer)'
+        d_in = dim_in
+        for i in range(num_layers // cfg.gnn.skip_every):
+            if cfg.gnn.stage_type == 'skipsum':
+                d_in = dim_in if i == 0 else dim_out
+            elif cfg.gnn.stage_type == 'skipconcat':
+                d_in = dim_in if i == 0 else dim_in + i * dim_out
+            self.add_module('block{}'.format(i), GNNSkipBlock(d_in, dim_out, cfg.gnn.skip_every))
+        self.dim_out = d_in + dim_out if cfg.gnn.stage_type == 'skipconcat' else dim_out
+
+    def forward(self, batch):
+        for layer in self.children():
+            batch = layer(batch)
+        if cfg.gnn.l2norm:
+            batch.node_feature = F.normalize(batch.node_feature, p=2, dim=-1)
+        return batch
+
+
+stage_dict = {'stack': GNNStackStage, 'skipsum': GNNSkipStage, 'skipconcat': GNNSkipStage}      # gnn.py:112-116
+
+
 class GNNNodeHead(nn.Module):
     """graphgym/models/head.py:19-37"""
 
@@ -309,21 +390,23 @@ head_dict = {'node': GNNNodeHead, 'graph': GNNGraphHead,      # head.py:122-127
 
 
 class GNN(nn.Module):
-    """graphgym/models/gnn.py:123-168 with stage_type 'stack' (the skip stages concatenate / add around the same
-    layers and are not on the path the BASELINE configs drive).  The feature-augmentation `preprocess` module of the
+    """graphgym/models/gnn.py:123-168: cfg.gnn.stage_type picks the message-passing stage from stage_dict — 'stack'
+    (mp.layer{i}), or 'skipsum' / 'skipconcat' (mp.block{i}.f.{j}: cfg.gnn.skip_every layers per block, the block's last
+    BatchNorm + skip add / concatenation + ReLU as one engine pass); an unknown key raises ValueError.  The feature-augmentation `preprocess` module of the
     reference holds no parameters and is outside the path: inputs arrive already assembled (the structural features and labels it
     concatenates: graphgym_amd.structure.augment)."""
 
     def __init__(self, dim_in, dim_out, **kwargs):
         super().__init__()
-        if getattr(cfg.gnn, "stage_type", "stack") != "stack":
-            raise ValueError("harness.GNN restates GNNStackStage only (cfg.gnn.stage_type = 'stack')")
+        stage_type = getattr(cfg.gnn, "stage_type", "stack")
+        if stage_type not in stage_dict:
+            raise ValueError("cfg.gnn.stage_type must be one of {}, got {!r}".format(sorted(stage_dict), stage_type))
         d_in = dim_in
         if cfg.gnn.layers_pre_mp > 0:
             self.pre_mp = GNNPreMP(d_in, cfg.gnn.dim_inner)
             d_in = cfg.gnn.dim_inner
         if cfg.gnn.layers_mp > 0:
-            self.mp = GNNStackStage(dim_in=d_in, dim_out=cfg.gnn.dim_inner, num_layers=cfg.gnn.layers_mp)
+            self.mp = stage_dict[stage_type](dim_in=d_in, dim_out=cfg.gnn.dim_inner, num_layers=cfg.gnn.layers_mp)
             d_in = self.mp.dim_out
         self.post_mp = head_dict[getattr(cfg.dataset, "task", "node")](dim_in=d_in, dim_out=dim_out)
 

@@ -122,6 +122,163 @@ def _bn_backward(ctx, dy, _dmean, _dinvstd, _dvar):
 register_autograd("mp::bn_act", _bn_backward, setup_context=_bn_setup)
 
 
+# ---- the skip block of the skipsum / skipconcat stages (graphgym/models/gnn.py:30-60) ---------------------------------
+# Behind a last layer built with has_act=False the block computes act(x + BN(h)) or act(cat(x, BN(h))).  As separate
+# passes that is BN statistics, BN apply, add / cat, activation: 8 N d elements moved (8 N d + 4 N d_skip for cat); the
+# engine's apply pass takes the skip operand and the activation along: 4 N d, or 3 N d + 2 N d_skip.
+SKIP_SUM, SKIP_CONCAT = 0, 1            # MP_BN_SKIP_SUM / MP_BN_SKIP_CONCAT of include/mp_engine.h
+_SKIP_MODES = {"sum": SKIP_SUM, "skipsum": SKIP_SUM, "concat": SKIP_CONCAT, "skipconcat": SKIP_CONCAT,
+               SKIP_SUM: SKIP_SUM, SKIP_CONCAT: SKIP_CONCAT}
+
+
+def _rows32(t):
+    """fp32 rows with unit column stride and a row stride that covers them (a column slice stays a view)"""
+    ok = t.dtype == torch.float32 and t.stride(-1) == 1 and t.stride(0) >= t.size(1)
+    return t if ok else t.float().contiguous()
+
+
+def _check_skip_shapes(x, skip, mode):
+    if mode not in (SKIP_SUM, SKIP_CONCAT):
+        raise ValueError(f"mode must be SKIP_SUM ({SKIP_SUM}) or SKIP_CONCAT ({SKIP_CONCAT}), got {mode}")
+    if x.dim() != 2 or skip.dim() != 2 or skip.size(0) != x.size(0):
+        raise ValueError(f"x and skip must be [N, d] and [N, d_skip], got {tuple(x.shape)} and {tuple(skip.shape)}")
+    if mode == SKIP_SUM and skip.size(1) != x.size(1):
+        raise ValueError(f"SKIP_SUM needs d_skip == d, got {skip.size(1)} and {x.size(1)}")
+
+
+def _skip_fake(x, skip, mode):
+    d = x.size(1)
+    width = d if mode == SKIP_SUM else skip.size(1) + d
+    return (x.new_empty((x.size(0), width), dtype=torch.float32), x.new_empty((d,), dtype=torch.float32),
+            x.new_empty((d,), dtype=torch.float32), x.new_empty((d,), dtype=torch.float32))
+
+
+@custom_op("mp::bn_skip_fwd_raw", mutates_args=(), device_types="cuda")
+def _op_bn_skip_fwd_raw(x: Tensor, skip: Tensor, weight: Optional[Tensor], bias: Optional[Tensor], eps: float,
+                        relu: bool, mode: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(out, mean, invstd, unbiased var): out = act(skip + BN(x)) [N, d] (SKIP_SUM) or [act(skip) | act(BN(x))]
+    [N, d_skip + d] (SKIP_CONCAT), BN over the node axis with batch statistics; one launch sequence"""
+    _require_hip(x, "x")
+    _require_hip(skip, "skip")
+    _check_skip_shapes(x, skip, mode)
+    x, skip = _rows32(x), _rows32(skip)
+    N, d = x.shape
+    d_skip = skip.size(1)
+    out = placement.empty_or_torch((N, d if mode == SKIP_SUM else d_skip + d), x.device, reads=(x, skip),
+                                   streaming=True)
+    mean = torch.empty(d, dtype=torch.float32, device=x.device)
+    invstd = torch.empty_like(mean)
+    var_u = torch.empty_like(mean)
+    w = None if weight is None else weight.detach().contiguous()
+    b = None if bias is None else bias.detach().contiguous()
+    with torch.cuda.device(x.device):
+        ws, nb = _bn_ws(N, d, x.device)
+        check(lib().mp_bn_train_fwd_skip_f32(ptr(x), x.stride(0), ptr(skip), skip.stride(0), N, d, d_skip, mode, ptr(w),
+                                             ptr(b), float(eps), 1 if relu else 0, ptr(out), out.stride(0), ptr(mean),
+                                             ptr(invstd), ptr(var_u), ptr(ws), nb, _stream()),
+              "mp_bn_train_fwd_skip_f32")
+    return out, mean, invstd, var_u
+
+
+@_op_bn_skip_fwd_raw.register_fake
+def _(x, skip, weight, bias, eps, relu, mode):
+    return _skip_fake(x, skip, mode)
+
+
+@custom_op("mp::bn_skip_bwd_raw", mutates_args=(), device_types="cuda")
+def _op_bn_skip_bwd_raw(dy: Tensor, out: Optional[Tensor], x: Tensor, weight: Optional[Tensor], mean: Tensor,
+                        invstd: Tensor, mode: int, want_dskip: bool = True) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(dx, dgamma, dbeta, dskip) of bn_skip_fwd_raw; out = the forward's result when it applied the ReLU, None when not.
+    SKIP_SUM: the statistics pass writes dskip = dy * [out > 0] and the apply pass reads it back (7 N d elements moved).
+    SKIP_CONCAT: mp_bn_train_bwd_f32 on the right-hand column views of dy and out; the left slab's mask is torch's.
+    Without the ReLU d(skip) is dy (its left slab) itself, and without want_dskip nobody asks: dskip then comes back
+    EMPTY (an operator cannot return a view of its input) and the caller takes dy."""
+    x = _rows32(x)
+    dy = _rows32(dy)
+    N, d = x.shape
+    d_skip = d if mode == SKIP_SUM else dy.size(1) - d
+    if mode not in (SKIP_SUM, SKIP_CONCAT) or d_skip <= 0 or dy.size(0) != N or (out is not None and out.shape != dy.shape):
+        raise ValueError(f"bn_skip_bwd_raw: dy {tuple(dy.shape)}, x {tuple(x.shape)}, mode {mode} do not fit")
+    out = None if out is None else _rows32(out)
+    dx = placement.empty_or_torch((N, d), x.device, reads=(dy, x), streaming=True)
+    dgamma = torch.empty(d, dtype=torch.float32, device=x.device)
+    dbeta = torch.empty_like(dgamma)
+    dskip = torch.empty(0, dtype=torch.float32, device=x.device)
+    w = None if weight is None else weight.detach().contiguous()
+    with torch.cuda.device(x.device):
+        ws, nb = _bn_ws(N, d, x.device)
+        if mode == SKIP_SUM and out is not None and want_dskip:
+            dskip = placement.empty_or_torch((N, d), x.device, reads=(dy, out), streaming=True)
+            check(lib().mp_bn_train_bwd_skip_f32(ptr(dy), dy.stride(0), ptr(out), out.stride(0), ptr(x), x.stride(0), N,
+                                                 d, ptr(w), ptr(mean), ptr(invstd), ptr(dx), dx.stride(0), ptr(dskip),
+                                                 dskip.stride(0), ptr(dgamma), ptr(dbeta), ptr(ws), nb, _stream()),
+                  "mp_bn_train_bwd_skip_f32")
+        else:
+            dyr = dy if mode == SKIP_SUM else dy[:, d_skip:]
+            yr = out if (out is None or mode == SKIP_SUM) else out[:, d_skip:]
+            check(lib().mp_bn_train_bwd_f32(ptr(dyr), dyr.stride(0), ptr(yr), yr.stride(0) if yr is not None else 0,
+                                            ptr(x), x.stride(0), N, d, ptr(w), ptr(mean), ptr(invstd), ptr(dx),
+                                            dx.stride(0), ptr(dgamma), ptr(dbeta), ptr(ws), nb, _stream()),
+                  "mp_bn_train_bwd_f32")
+            if mode == SKIP_CONCAT and out is not None and want_dskip:
+                dskip = _masked(dy[:, :d_skip], out[:, :d_skip])
+    return dx, dgamma, dbeta, dskip
+
+
+@_op_bn_skip_bwd_raw.register_fake
+def _(dy, out, x, weight, mean, invstd, mode, want_dskip=True):
+    d = x.size(1)
+    n_skip = 0 if (out is None or not want_dskip) else (d if mode == SKIP_SUM else dy.size(1) - d)
+    dskip = x.new_empty((x.size(0), n_skip), dtype=torch.float32) if n_skip else x.new_empty((0,), dtype=torch.float32)
+    return (x.new_empty(x.shape, dtype=torch.float32), x.new_empty((d,), dtype=torch.float32),
+            x.new_empty((d,), dtype=torch.float32), dskip)
+
+
+def _masked(dy, out):
+    """dy * [out > 0] as the kernels write it (a masked element is +0, whatever dy's sign)"""
+    return torch.where(out > 0, dy, dy.new_zeros(()))
+
+
+@custom_op("mp::bn_skip_act", mutates_args=(), device_types="cuda")
+def _op_bn_skip_act(x: Tensor, skip: Tensor, weight: Optional[Tensor], bias: Optional[Tensor], eps: float, relu: bool,
+                    mode: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """graphgym/models/gnn.py:49-60 behind a last layer without activation, in training mode: act(skip + BN(x)) or
+    act(cat(skip, BN(x))): (out, mean, invstd, var)"""
+    return torch.ops.mp.bn_skip_fwd_raw(x, skip, weight, bias, eps, relu, mode)
+
+
+@_op_bn_skip_act.register_fake
+def _(x, skip, weight, bias, eps, relu, mode):
+    return _skip_fake(x, skip, mode)
+
+
+def _bn_skip_setup(ctx, inputs, output):
+    x, skip, weight, bias, eps, relu, mode = inputs
+    out, mean, invstd, _ = output
+    ctx.relu, ctx.mode, ctx.d_skip = relu, mode, skip.size(1)
+    ctx.has_affine = (weight is not None, bias is not None)
+    # skip is not kept: its gradient is the masked dy, and the mask is out's (kept only when there is one)
+    ctx.save_for_backward(x, out if relu else None, weight, mean, invstd)
+
+
+def _bn_skip_backward(ctx, dy, _dmean, _dinvstd, _dvar):
+    x, out, w, mean, invstd = ctx.saved_tensors
+    need_x, need_skip, need_w, need_b = ctx.needs_input_grad[:4]
+    dx = dgamma = dbeta = dskip = None
+    left = (lambda t: t) if ctx.mode == SKIP_SUM else (lambda t: t[:, :ctx.d_skip])
+    if need_x or need_w or need_b:
+        dx, dgamma, dbeta, g = torch.ops.mp.bn_skip_bwd_raw(dy, out, x, w, mean, invstd, ctx.mode, need_skip)
+        if need_skip:
+            dskip = left(dy) if out is None else g
+    elif need_skip:             # no BatchNorm backward at all
+        dskip = left(dy) if out is None else _masked(left(dy), left(out))
+    return (dx if need_x else None, dskip, dgamma if (need_w and ctx.has_affine[0]) else None,
+            dbeta if (need_b and ctx.has_affine[1]) else None, None, None, None)
+
+
+register_autograd("mp::bn_skip_act", _bn_skip_backward, setup_context=_bn_skip_setup)
+
+
 # ---- softmax cross-entropy over the labelled rows (graphgym/loss.py:53-68, 20-37) -------------------------------
 def _check_ce_shapes(z, y, idx):
     """host-side shape contract (no device read): one label per selected row.  Label VALUES are checked on the device:
@@ -210,6 +367,16 @@ def softmax_cross_entropy(logits, labels, index=None):
     return torch.ops.mp.softmax_ce(logits, labels, index)
 
 
+def _update_running_stats(bn, mean, var_u):
+    """torch.nn.BatchNorm1d's training-mode bookkeeping from the batch mean and unbiased variance"""
+    if bn.training and bn.track_running_stats:
+        with torch.no_grad():
+            bn.num_batches_tracked += 1
+            m = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
+            bn.running_mean.mul_(1 - m).add_(mean, alpha=m)
+            bn.running_var.mul_(1 - m).add_(var_u, alpha=m)
+
+
 class BatchNorm1d(nn.BatchNorm1d):
     """``nn.BatchNorm1d`` whose training-mode forward / backward run on the engine; ``relu=True`` fuses the
     activation that follows it in GraphGym's layer wrapper.  Eval mode uses the running statistics (torch)."""
@@ -227,16 +394,35 @@ class BatchNorm1d(nn.BatchNorm1d):
             y = super().forward(x)
             return torch.relu(y) if self.relu else y
         y, mean, _, var_u = torch.ops.mp.bn_act(x, self.weight, self.bias, float(self.eps), bool(self.relu))
-        if self.training and self.track_running_stats:
-            with torch.no_grad():
-                self.num_batches_tracked += 1
-                m = self.momentum if self.momentum is not None else 1.0 / float(self.num_batches_tracked)
-                self.running_mean.mul_(1 - m).add_(mean, alpha=m)
-                self.running_var.mul_(1 - m).add_(var_u, alpha=m)
+        _update_running_stats(self, mean, var_u)
         return y
 
     def extra_repr(self):
         return super().extra_repr() + f", relu={self.relu}"
+
+
+def bn_skip_act(bn, x, skip, mode, relu=True, act=None):
+    """The tail of GraphGym's skip block (graphgym/models/gnn.py:49-60) around its last layer's BatchNorm:
+    ``act(skip + bn(x))`` for mode "skipsum" / SKIP_SUM, ``act(cat((skip, bn(x)), 1))`` for "skipconcat" / SKIP_CONCAT,
+    with act = ReLU (``relu=True``), nothing (``relu=False``) or a callable ``act``.
+
+    `bn` is a ``torch.nn.BatchNorm1d`` or this module's BatchNorm1d; its parameters are used and its running statistics
+    updated exactly as its own forward would.  With batch statistics on fp32 device tensors and ReLU or no activation
+    this is one engine op (mp::bn_skip_act: statistics, then one pass that normalises, adds or places the skip operand
+    and activates); everything else — eval mode with running statistics, CPU tensors, bf16, a single row, another
+    activation, a BatchNorm that carries its own fused ReLU — is the torch composition, the rule of BatchNorm1d.forward."""
+    mode = _SKIP_MODES[mode]
+    _check_skip_shapes(x, skip, mode)
+    use_batch_stats = bn.training or not bn.track_running_stats
+    if not (act is None and isinstance(bn, nn.BatchNorm1d) and not getattr(bn, "relu", False) and use_batch_stats
+            and x.is_cuda and skip.is_cuda and x.size(0) > 1 and x.dtype != torch.bfloat16
+            and skip.dtype != torch.bfloat16):
+        y = bn(x)
+        z = skip + y if mode == SKIP_SUM else torch.cat((skip, y), 1)
+        return act(z) if act is not None else (torch.relu(z) if relu else z)
+    out, mean, _, var_u = torch.ops.mp.bn_skip_act(x, skip, bn.weight, bn.bias, float(bn.eps), bool(relu), mode)
+    _update_running_stats(bn, mean, var_u)
+    return out
 
 
 class _NarrowHead(torch.autograd.Function):

@@ -322,6 +322,27 @@ int mp_bn_train_bwd_relu_f32(const float* dy, int64_t lddy, const float* x, int6
                              const float* gamma, const float* beta, const float* mean, const float* invstd,
                              float* dx, int64_t lddx, float* dgamma, float* dbeta, void* ws, size_t ws_bytes,
                              mp_stream_t stream);
+/* The skip block of GraphGym's skipsum / skipconcat stages (graphgym/models/gnn.py:30-60) behind a last layer without
+ * activation, with the statistics and workspace of mp_bn_train_fwd_f32 and ONE apply launch:
+ *   MP_BN_SKIP_SUM    (d_skip == d): out[N, d]          = act(skip + BN(x))
+ *   MP_BN_SKIP_CONCAT              : out[N, d_skip + d] = [act(skip) | act(BN(x))]
+ * act = ReLU when relu != 0.  BN(x) is mp_bn_train_fwd_f32's own expression: with skip == 0 (SUM), or in the right
+ * slab (CONCAT), out equals its y.  A launch takes its 4-wide form when every pointer it forms is 16-byte aligned and
+ * every stride a multiple of 4 (CONCAT: out + d_skip included).
+ *   bwd (SUM): g = dy * [out > 0] is written to dskip by the statistics pass and read back by the apply pass (7 N d
+ *   elements moved instead of 8); dx, dgamma, dbeta are mp_bn_train_bwd_f32(dy, y = out, ...)'s bits.  out NULL = no
+ *   activation: d(skip) is dy itself, dskip is not written and may be NULL.
+ *   bwd (CONCAT): mp_bn_train_bwd_f32 on the column views dy + d_skip, out + d_skip. */
+#define MP_BN_SKIP_SUM 0
+#define MP_BN_SKIP_CONCAT 1
+int mp_bn_train_fwd_skip_f32(const float* x, int64_t ldx, const float* skip, int64_t ldskip, int64_t N, int32_t d,
+                             int32_t d_skip, int mode, const float* gamma, const float* beta, float eps, int relu,
+                             float* out, int64_t ldo, float* mean, float* invstd, float* var_unbiased, void* ws,
+                             size_t ws_bytes, mp_stream_t stream);
+int mp_bn_train_bwd_skip_f32(const float* dy, int64_t lddy, const float* out, int64_t ldo, const float* x, int64_t ldx,
+                             int64_t N, int32_t d, const float* gamma, const float* mean, const float* invstd,
+                             float* dx, int64_t lddx, float* dskip, int64_t lddskip, float* dgamma, float* dbeta,
+                             void* ws, size_t ws_bytes, mp_stream_t stream);
 
 /* ------------------------------------------------------------------ *
  * Aggregate -> transform in one kernel                                *
