@@ -13,7 +13,10 @@ def _defaults():
     cfg.device = "auto"                      # config.py:33
     cfg.num_threads = 6                      # config.py:57
     cfg.dataset = types.SimpleNamespace(transform="none", augment_feature=[], task="node",
-                                        edge_dim=128)                    # config.py:145
+                                        edge_dim=128,                    # config.py:145
+                                        edge_train_mode="all", edge_message_ratio=0.8,
+                                        edge_negative_sampling_ratio=1.0, resample_disjoint=False,
+                                        resample_negative=False)         # config.py:147-163 (link_pred.py)
     cfg.model = types.SimpleNamespace(graph_pooling="add", loss_fun="cross_entropy")      # config.py:285-301
     cfg.train = types.SimpleNamespace(batch_size=16)
     cfg.gnn = types.SimpleNamespace(

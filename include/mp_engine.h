@@ -725,6 +725,37 @@ int mp_hop_distances(const int32_t* rowptr, const int32_t* col, int64_t N, int64
                      int64_t n_pairs, int32_t* dist, mp_stream_t stream);
 
 /* ------------------------------------------------------------------ *
+ * Link-prediction labels: the pair space of a batch and a sampler of   *
+ * distinct non-edges (GraphGym's edge_negative_sampling_ratio and      *
+ * resample_negative, graphgym/config.py:147-163).  The base CSR as     *
+ * above (row = destination, columns ascending inside a row), no column *
+ * twice in a row; graph g = nodes graph_ptr[g] .. graph_ptr[g+1]       *
+ * (device, int64).  A candidate pair lies inside one graph:            *
+ *   MP_PAIRS_UNDIRECTED  (r, c) with c > r: every unordered pair once; *
+ *   MP_PAIRS_DIRECTED    (src = c, dst = r) with c != r.               *
+ * N or nnz >= 2^31: MP_ERR_UNSUPPORTED.  Nothing is allocated, no       *
+ * synchronisation.                                                     *
+ * ------------------------------------------------------------------ */
+enum mp_pair_mode { MP_PAIRS_UNDIRECTED = 0, MP_PAIRS_DIRECTED = 1 };
+/* free_out[r] <- the number of candidate partners of row r that the row does not store (a stored diagonal entry is no
+ * candidate in either mode).  flags [2] (device, zeroed by the call): flags[0] <- 1 if a row stores a column twice,
+ * flags[1] <- 1 if a row stores a column outside its graph; free_out is meaningless then. */
+int mp_pair_space_rows(const int32_t* rowptr, const int32_t* col, int64_t N, int64_t nnz,
+                       const int64_t* graph_ptr, int64_t n_graphs, int32_t mode, int64_t* free_out,
+                       int32_t* flags, mp_stream_t stream);
+/* Draws K_g = slot_base[g+1] - slot_base[g] distinct non-edges of every graph g: sample i of graph g goes to slot
+ * slot_base[g] + i of out [2, K] (global ids; row 0 = src, row 1 = dst; undirected pairs as (r, c), r < c).  prefix
+ * [N+1] is the exclusive prefix sum of mp_pair_space_rows' free_out (prefix[N] = the total); C_g = prefix[graph_ptr[g+1]]
+ * - prefix[graph_ptr[g]] and the caller guarantees K_g <= C_g (a slot beyond C_g receives (-1, -1)).  The non-edges of
+ * a graph in (row, column) order are numbered 0 .. C_g - 1 and sample i is number perm_g(i), perm_g a keyed bijection
+ * of [0, C_g) (a 6-round balanced Feistel network with cycle walking, keys from (seed, offset, g)): no rejection, no
+ * repeated pair, K_g = C_g returns the whole complement, and sample i does not depend on K. */
+int mp_sample_non_edges(const int32_t* rowptr, const int32_t* col, int64_t N, int64_t nnz,
+                        const int64_t* graph_ptr, int64_t n_graphs, const int64_t* prefix,
+                        const int64_t* slot_base, int64_t K, int32_t mode, uint64_t seed, uint64_t offset,
+                        int64_t* out, mp_stream_t stream);
+
+/* ------------------------------------------------------------------ *
  * Structural labels and features (graphgym/models/feature_augment.py)  *
  * The engine's CSR, columns ascending inside a row.  Integer results:  *
  * bit-reproducible.  Nothing is allocated, no synchronisation.         *
