@@ -99,9 +99,6 @@ PROTOTYPES = {
     "mp_edge_att_alpha_f32": (C.c_int, [_p, _p, _p, _i64, _i64, _i32, _p, _p, _p, _f32, _p, _p]),
     "mp_csr_row_softmax_f32": (C.c_int, [_p, _i64, _i32, _p, _p, _p]),
     "mp_csr_row_softmax_bwd_f32": (C.c_int, [_p, _i64, _i32, _p, _p, _p, _p]),
-    "mp_sddmm_grad_f32": (C.c_int, [_p, _p, _i64, _i64, _p, _i64, _p, _i64, _i32, _i32, _p, _p]),
-    "mp_spmm_csr_heads_f32": (C.c_int, [_p, _p, _p, _i64, _p, _pi32, _i32, _p, _i64, _p, _i64, _i32, _p, _sz, _p]),
-    "mp_spmm_heads_f32": (C.c_int, [_p, _p, _p, _i64, _i32, _p, _i64, _p, _i64, _i32, _p]),
     "mp_spmm_csr_heads_reduce_f32": (C.c_int, [_p, _p, _p, _i64, _p, _pi32, _i32, C.c_int, _p, _i64, _p, _i64, _i32, _p, _p, _sz, _p]),
     "mp_spmm_csr_edge_f32": (C.c_int, [_p, _p, _p, _p, _i64, _p, _pi32, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _i32, C.c_int,
                                        _p, _p, _p, _sz, _p]),

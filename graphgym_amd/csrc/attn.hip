@@ -1,5 +1,5 @@
-// Per-edge attention pieces for the GAT layers (K12-K14): SDDMM scores, softmax
-// over each destination row's entries, and the multi-head weighted aggregation.
+// Per-edge attention pieces for the GAT layers (K12-K14): SDDMM scores and the softmax
+// over each destination row's entries (the multi-head weighted aggregation is spmm.hip's).
 //   dot-product form   gat_id                TfgIDLayer.py:297-355
 //   additive form      GATIDConvLayer        idconv.py:317-332
 //   segment softmax    SparseAdj.softmax     sparse_adj.py:136-151
@@ -478,35 +478,6 @@ __global__ __launch_bounds__(kBlock) void row_softmax_bwd_kernel(const int32_t* 
     });
 }
 
-// Y[r, c] = sum_e a[e*H + c/dh] * V[col[e], c]
-__global__ __launch_bounds__(kBlock) void spmm_heads_kernel(const int32_t* __restrict__ rowptr,
-                                                            const int32_t* __restrict__ col,
-                                                            const float* __restrict__ a, int64_t N,
-                                                            int32_t heads, const float* __restrict__ V,
-                                                            int64_t ldv, float* Y, int64_t ldy, int32_t d) {
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int dh = d / heads;
-  for (int64_t r = (int64_t)blockIdx.x * kWavesPerBlock + wave; r < N;
-       r += (int64_t)gridDim.x * kWavesPerBlock) {
-    const int e0 = rowptr[r], e1 = rowptr[r + 1];
-    for (int c = lane; c < d; c += kWave) {
-      const int h = c / dh;
-      float acc = 0.f;
-      for (int e = e0; e < e1; ++e)
-        acc = fmaf(a[(int64_t)e * heads + h], V[(int64_t)col[e] * ldv + c], acc);
-      Y[r * ldy + c] = acc;
-    }
-  }
-}
-
-static int row_grid(int64_t N) {
-  int64_t b = ceil_div(N, kWavesPerBlock);
-  if (b < 1) b = 1;
-  if (b > kNumCU * 16) b = kNumCU * 16;
-  return (int)b;
-}
-
 static bool al(const void* p, size_t a) { return ((uintptr_t)p % a) == 0; }
 
 // the entry-balanced launch of both forms: widest vector every operand allows, no wider than the row needs
@@ -578,12 +549,6 @@ int mp_spmm_heads_max_da_f32(const int32_t* row_of, const int32_t* col, int64_t 
                                    as_stream(stream));
 }
 
-int mp_sddmm_grad_f32(const int32_t* rowptr, const int32_t* col, int64_t N, int64_t nnz, const float* A,
-                      int64_t lda, const float* B, int64_t ldb, int32_t d, int32_t heads, float* g,
-                      mp_stream_t stream) {
-  return mp_sddmm_dot_f32(rowptr, col, N, nnz, A, lda, B, ldb, d, heads, 1.0f, g, stream);
-}
-
 int mp_sddmm_add_f32(const int32_t* rowptr, const int32_t* col, int64_t N, int64_t nnz, const float* ai,
                      const float* aj, float slope, float* s, mp_stream_t stream) {
   if (!rowptr || N < 0 || nnz < 0) return MP_ERR_INVALID_ARG;
@@ -639,17 +604,6 @@ int mp_csr_row_softmax_bwd_f32(const int32_t* rowptr, int64_t N, int32_t heads, 
   if (!p || !dp || !ds) return MP_ERR_INVALID_ARG;
   hipLaunchKernelGGL(row_softmax_bwd_kernel, dim3(flat_grid(N)), dim3(kBlock), 0, as_stream(stream), rowptr, N,
                      heads, p, dp, ds);
-  MP_LAUNCH_CHECK();
-  return MP_OK;
-}
-
-int mp_spmm_heads_f32(const int32_t* rowptr, const int32_t* col, const float* a, int64_t N, int32_t heads,
-                      const float* V, int64_t ldv, float* Y, int64_t ldy, int32_t d, mp_stream_t stream) {
-  if (!rowptr || N < 0 || heads <= 0 || d <= 0 || d % heads) return MP_ERR_INVALID_ARG;
-  if (N == 0) return MP_OK;
-  if (!Y || !V || ldv < d || ldy < d) return MP_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(spmm_heads_kernel, dim3(row_grid(N)), dim3(kBlock), 0, as_stream(stream), rowptr, col, a,
-                     N, heads, V, ldv, Y, ldy, d);
   MP_LAUNCH_CHECK();
   return MP_OK;
 }

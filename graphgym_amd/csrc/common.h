@@ -78,6 +78,14 @@ static inline int flat_grid(int64_t n) {
   return (int)b;
 }
 
+// grid for a kernel whose waves each take one row (or one 64-entry chunk) of N and stride on
+static inline int row_grid(int64_t N) {
+  int64_t b = ceil_div(N, kWavesPerBlock);
+  if (b < 1) b = 1;
+  if (b > kNumCU * 16) b = kNumCU * 16;
+  return (int)b;
+}
+
 // ---- plan blob layout (int32 words) -------------------------------------
 constexpr int32_t kPlanMagic = 0x4D50504C;
 enum PlanWord {

@@ -686,7 +686,7 @@ int mp_ego_expand(const int32_t* rowptr, const int32_t* col, int64_t N, const in
   EGO_LAUNCH_CHECK();
   EGO_TAKE(cnt, int32_t, (size_t)M * 4);
   EGO_TAKE(eoff, int64_t, (size_t)(M + 1) * 8);
-  const dim3 egrid((unsigned)(ceil_div(M, kWavesPerBlock) < kNumCU * 16 ? ceil_div(M, kWavesPerBlock) : kNumCU * 16));
+  const dim3 egrid(row_grid(M));
   // one workgroup per (ego, chunk of its members): chunk_off[c] = chunks of the egos before c; the grid is the bound
   // M / chunk + B, workgroups past chunk_off[B] leave at once
   constexpr int kChunk = 128;

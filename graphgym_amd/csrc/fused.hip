@@ -391,8 +391,7 @@ __global__ __launch_bounds__(kBlock) void id_fixup_kernel(const int32_t* __restr
 template <bool SET>
 static int launch_id_fixup(const int32_t* rows, const int32_t* crp, const int32_t* slot, const float* val, int64_t n_rows,
                            const float* Z, int64_t ldz, float* out, int64_t ldo, int32_t d, int act, hipStream_t st) {
-  int blocks = (int)ceil_div(n_rows, kWavesPerBlock);
-  if (blocks > kNumCU * 16) blocks = kNumCU * 16;
+  const int blocks = row_grid(n_rows);
   const bool v4 = d % 4 == 0 && ldz % 4 == 0 && ldo % 4 == 0 && ((uintptr_t)Z % 16) == 0 && ((uintptr_t)out % 16) == 0;
   if (v4)
     hipLaunchKernelGGL((id_fixup_kernel<4, SET>), dim3(blocks), dim3(kBlock), 0, st, rows, crp, slot, val,

@@ -996,14 +996,6 @@ int mp_idgnn_agg_f32(const int32_t* rowptr, const int32_t* col_marked, const flo
                          nullptr, 0, 0.f, nullptr, MP_ACT_NONE, nullptr, ws, ws_bytes, as_stream(stream));
 }
 
-int mp_spmm_csr_heads_f32(const int32_t* rowptr, const int32_t* col, const float* a, int64_t N, const int32_t* plan,
-                          const int32_t* counts_host, int32_t heads, const float* V, int64_t ldv, float* Y, int64_t ldy,
-                          int32_t d, void* ws, size_t ws_bytes, mp_stream_t stream) {
-  if (heads < 1 || !a) return MP_ERR_INVALID_ARG;
-  return agg_common<F32>(rowptr, col, a, N, plan, counts_host, V, ldv, Y, ldy, nullptr, 0, d, MP_SUM, nullptr, 0, 0.f,
-                         nullptr, MP_ACT_NONE, nullptr, ws, ws_bytes, as_stream(stream), nullptr, 0, 1e-12f, heads);
-}
-
 int mp_spmm_csr_heads_reduce_f32(const int32_t* rowptr, const int32_t* col, const float* a, int64_t N,
                                  const int32_t* plan, const int32_t* counts_host, int32_t heads, int reduce,
                                  const float* V, int64_t ldv, float* Y, int64_t ldy, int32_t d, int32_t* argmax,
@@ -1021,9 +1013,7 @@ int mp_spmm_heads_max_bwd_f32(const int32_t* col, const float* a, int32_t heads,
   if (ldy < d || ldv < d) return MP_ERR_INVALID_ARG;
   if (N >= INT32_MAX) return MP_ERR_UNSUPPORTED;
   if (N == 0) return MP_OK;
-  int64_t blocks = ceil_div(N, kWavesPerBlock);
-  if (blocks > kNumCU * 16) blocks = kNumCU * 16;
-  hipLaunchKernelGGL(heads_max_bwd_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), col, a, heads,
+  hipLaunchKernelGGL(heads_max_bwd_kernel, dim3(row_grid(N)), dim3(kBlock), 0, as_stream(stream), col, a, heads,
                      d / heads, argmax, dY, ldy, N, d, dV, ldv);
   MP_LAUNCH_CHECK();
   return MP_OK;
@@ -1065,23 +1055,21 @@ static int edge_bwd_launch(const int32_t* rowptr, const int32_t* eid, const floa
   if (N == 0 || nnz == 0) return MP_OK;
   const int32_t hw = heads > 1 ? d / heads : d;
   if (reduce == MP_MAX) {
-    int64_t blocks = ceil_div(N, kWavesPerBlock);
-    if (blocks > kNumCU * 16) blocks = kNumCU * 16;
+    const dim3 grid(row_grid(N));
     if (heads > 1)
-      hipLaunchKernelGGL(edge_bwd_max_kernel<true>, dim3((unsigned)blocks), dim3(kBlock), 0, st, eid, val, heads, hw,
+      hipLaunchKernelGGL(edge_bwd_max_kernel<true>, grid, dim3(kBlock), 0, st, eid, val, heads, hw,
                          argmax, N, dY, ldy, d, dM, ldm);
     else
-      hipLaunchKernelGGL(edge_bwd_max_kernel<false>, dim3((unsigned)blocks), dim3(kBlock), 0, st, eid, val, 1, hw,
+      hipLaunchKernelGGL(edge_bwd_max_kernel<false>, grid, dim3(kBlock), 0, st, eid, val, 1, hw,
                          argmax, N, dY, ldy, d, dM, ldm);
   } else {
-    int64_t blocks = ceil_div(ceil_div(nnz, kWave), kWavesPerBlock);
-    if (blocks > kNumCU * 16) blocks = kNumCU * 16;
+    const dim3 grid(row_grid(ceil_div(nnz, kWave)));
     const int mean = reduce == MP_MEAN ? 1 : 0;
     if (heads > 1)
-      hipLaunchKernelGGL(edge_bwd_rows_kernel<true>, dim3((unsigned)blocks), dim3(kBlock), 0, st, rowptr, eid, val,
+      hipLaunchKernelGGL(edge_bwd_rows_kernel<true>, grid, dim3(kBlock), 0, st, rowptr, eid, val,
                          heads, hw, (int32_t)N, (int32_t)nnz, mean, dY, ldy, d, dM, ldm);
     else
-      hipLaunchKernelGGL(edge_bwd_rows_kernel<false>, dim3((unsigned)blocks), dim3(kBlock), 0, st, rowptr, eid, val, 1,
+      hipLaunchKernelGGL(edge_bwd_rows_kernel<false>, grid, dim3(kBlock), 0, st, rowptr, eid, val, 1,
                          hw, (int32_t)N, (int32_t)nnz, mean, dY, ldy, d, dM, ldm);
   }
   MP_LAUNCH_CHECK();

@@ -31,7 +31,7 @@ __global__ __launch_bounds__(kBlock) void read_probe_kernel(const cp_f32x4* __re
 
 extern "C" {
 
-int mp_version(void) { return 100; }
+int mp_version(void) { return 101; }
 
 int mp_read_probe_f32(const float* src, int64_t n, float* sink, mp_stream_t stream) {
   if (n < 0 || !sink || (n > 0 && !src) || n % 4 || ((uintptr_t)src % 16)) return MP_ERR_INVALID_ARG;

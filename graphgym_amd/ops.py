@@ -543,40 +543,87 @@ def _raw_sddmm_dot(g, A, B, heads, scale, idx=None):
     return s[:g.nnz * heads].view(g.nnz, heads)
 
 
-def _raw_spmm_heads(g, a, V, heads):
-    if heads == 1:   # one weight per entry: this is the hot aggregation kernel with val = a
-        y, _ = _raw_spmm(g.with_values(a.reshape(-1).contiguous()), V, _lib.SUM)
-        return y
-    if heads in (2, 4, 8) and V.size(1) % heads == 0:
-        # all heads in ONE launch of the hot kernel: full-row loads of V, every lane applies the weight of the head its
-        # columns belong to (mp_spmm_csr_heads_f32); round 1 ran one launch per head on column slices
+HEADS_ONE_LAUNCH = (2, 4, 8)     # head counts of mp_spmm_csr_heads_reduce_f32 / mp_spmm_csr_edge_heads_f32 beside 1
+
+
+def _raw_heads_agg(g, w, x, heads, reduce=_lib.SUM, want_argmax=False, edge=None, one_launch=True):
+    """y[r, slice h] = reduce_e w[e, h] x[col_e, slice h] -> (y, argmax [N, d] int32 or None); with edge = (m, t, bias)
+    the message is (x[col_e] + m[eid_e] + t[r])[slice h] and bias is added (m [E, d] by the entry's input position, t
+    [N, d] or None, bias [d] or None).  The ladder over the head count, once for both forms:
+      1 head            the aggregation itself with val = w (_raw_spmm — so a large sum still goes to the tile kernels — or
+                        _raw_spmm_edge)
+      2, 4 or 8 heads   one launch: full-row loads, every lane applies the weight of the head its columns belong to
+                        (mp_spmm_csr_heads_reduce_f32 / mp_spmm_csr_edge_heads_f32)
+      other counts, or a head layout the one launch does not take (status 2): the one-head call per head on column slices
+    one_launch=False sends 2, 4 and 8 heads through the per-head form too (tests, tests/perf/bench_edgeatt.py): the same
+    terms in the same order, the same bits, and the slower form as this function runs it — by 1.5 % on 2e7 entries,
+    where the copies of w's columns cost more than the H launches save, and threefold on 2e5 entries.
+    The entry values of g take no part: they belong in w."""
+    N, d = g.num_nodes, x.size(1)
+    if heads < 1 or d % heads:
+        raise ValueError(f"{'V' if edge is None else 'x'} has {d} columns, not a multiple of heads = {heads}")
+    m = t = bias = eid = None
+    if edge is not None:
+        m, t, bias = edge
+        eid = _eid_checked(g, m.size(0))
+        if m.size(0) == 0:      # every entry is an inserted loop: the kernel still reads (and drops) row 0
+            m = torch.zeros((1, d), dtype=torch.float32, device=x.device)
+
+    def one_head(vals, cs=slice(None), out=None):
+        gh = g.with_values(vals.contiguous())
+        if edge is None:
+            return _raw_spmm(gh, x[:, cs], reduce, want_argmax=want_argmax, out=out)
+        gh.__dict__["_eid_max"] = g.__dict__.get("_eid_max")     # (checked on g above: no second read of it per head)
+        return _raw_spmm_edge(gh, x[:, cs], m[:, cs], None if t is None else t[:, cs],
+                              None if bias is None else bias[cs], reduce, want_argmax, out=out)
+
+    if heads == 1:
+        return one_head(w.reshape(-1))
+    y = placement.empty_or_torch((N, d), x.device, reads=(x,) if edge is None else (x, m))
+    argmax = torch.empty((N, d), dtype=torch.int32, device=x.device) if want_argmax else None
+    if one_launch and heads in HEADS_ONE_LAUNCH:
         L = lib()
-        N, d = g.num_nodes, V.size(1)
-        a = a.contiguous()
-        y = placement.empty_or_torch((N, d), V.device, reads=(V,))
-        plan, counts, ws, ws_bytes = _plan_ws(g, V.device, d, _lib.SUM, False)
-        with torch.cuda.device(V.device):
-            st = L.mp_spmm_csr_heads_f32(ptr(g.rowptr), ptr(g.col), ptr(a), N, ptr(plan), counts, heads, ptr(V),
-                                         V.stride(0), ptr(y), y.stride(0), d, ptr(ws), ws_bytes, _stream())
-        if st == 0:
-            return y
+        w = w.contiguous()
+        plan, counts, ws, ws_bytes = _plan_ws(g, x.device, d, reduce, False)
+        with torch.cuda.device(x.device):
+            if edge is None:
+                name = "mp_spmm_csr_heads_reduce_f32"
+                st = L.mp_spmm_csr_heads_reduce_f32(ptr(g.rowptr), ptr(g.col), ptr(w), N, ptr(plan), counts, heads,
+                                                    reduce, ptr(x), x.stride(0), ptr(y), y.stride(0), d, ptr(argmax),
+                                                    ptr(ws), ws_bytes, _stream())
+            else:
+                name = "mp_spmm_csr_edge_heads_f32"
+                st = L.mp_spmm_csr_edge_heads_f32(ptr(g.rowptr), ptr(g.col), ptr(eid), ptr(w), N, ptr(plan), counts,
+                                                  heads, ptr(x), x.stride(0), ptr(m), m.stride(0), ptr(t),
+                                                  t.stride(0) if t is not None else 0, ptr(y), y.stride(0), d, reduce,
+                                                  ptr(bias), ptr(argmax), ptr(ws), ws_bytes, _stream())
         if st != 2:
-            check(st, "mp_spmm_csr_heads_f32")
-    if V.size(1) % heads == 0:
-        # head layouts outside the one-launch kernel: one launch of the hot kernel per head on column slices
-        dh = V.size(1) // heads
-        y = torch.empty((g.num_nodes, V.size(1)), dtype=torch.float32, device=V.device)
-        for h in range(heads):
-            _raw_spmm(g.with_values(a[:, h].contiguous()), V[:, h * dh:(h + 1) * dh], _lib.SUM,
-                      out=y[:, h * dh:(h + 1) * dh])
-        return y
-    L = lib()
-    y = torch.empty((g.num_nodes, V.size(1)), dtype=torch.float32, device=V.device)
-    with torch.cuda.device(V.device):
-        check(L.mp_spmm_heads_f32(ptr(g.rowptr), ptr(g.col), ptr(a), g.num_nodes, heads, ptr(V),
-                                  V.stride(0), ptr(y), y.stride(0), V.size(1), _stream()),
-              "mp_spmm_heads_f32")
-    return y
+            check(st, name)
+            return y, argmax
+    g.plan()                                     # built once, shared by the per-head graphs below
+    dh = d // heads
+    for h in range(heads):
+        cs = slice(h * dh, (h + 1) * dh)
+        _, am = one_head(w[:, h], cs, out=y[:, cs])
+        if want_argmax:
+            argmax[:, cs] = am
+    return y, argmax
+
+
+# the ladder under the names and argument orders the callers use
+def _raw_spmm_heads(g, a, V, heads):
+    """y[i, slice h] = sum_e a[e,h] V[col_e, slice h]"""
+    return _raw_heads_agg(g, a, V, heads)[0]
+
+
+def _raw_spmm_heads_reduce(g, a, V, heads, reduce):
+    """sum / mean / max of a[e,h] V[col_e, slice h] over each row -> (y, argmax [N, d] int32 for max, else None)"""
+    return _raw_heads_agg(g, a, V, heads, reduce, want_argmax=reduce == _lib.MAX)
+
+
+def _raw_spmm_edge_heads(g, w, x, m, t=None, bias=None, heads=1, reduce=_lib.SUM, want_argmax=False, one_launch=True):
+    """the two-gather form: reduce_e w[e, h] (x[col_e] + m[eid_e] + t[r])[slice h] + bias -> (y, argmax or None)"""
+    return _raw_heads_agg(g, w, x, heads, reduce, want_argmax, edge=(m, t, bias), one_launch=one_launch)
 
 
 class _SddmmDot(torch.autograd.Function):
@@ -636,6 +683,50 @@ def sddmm_add(g, ai, aj, slope=0.2):
     return _SddmmAdd.apply(ai, aj, g, float(slope))
 
 
+def _raw_row_softmax_bwd(g, p, dp):
+    """ds = p * (dp - sum over the row of p * dp), per head (mp_csr_row_softmax_bwd_f32); p, dp [nnz, H]"""
+    p, dp = p.contiguous(), dp.contiguous()
+    ds = torch.empty_like(p)
+    if g.nnz:
+        with torch.cuda.device(p.device):
+            check(lib().mp_csr_row_softmax_bwd_f32(ptr(g.rowptr), g.num_nodes, p.size(1), ptr(p), ptr(dp), ptr(ds),
+                                                   _stream()), "mp_csr_row_softmax_bwd_f32")
+    return ds
+
+
+_EA_DST, _EA_SRC, _EA_EDGE = 1, 2, 4
+
+
+def _alpha_bwd(g, alpha, dalpha, a_dst, a_src, a_edge, slope, which):
+    """(d_dst, d_src, d_edge) of the additive coefficients alpha = softmax_row(leaky_relu(a_dst[row] + a_src[col] +
+    a_edge[eid])) (gat_alpha: a_edge None; edge_att_alpha: a_dst may be None), each computed when its bit of `which`
+    (1, 2, 4) is set and its term exists, None otherwise: the row softmax backward, the slope mask on the recomputed
+    pre-activation, sums by destination and by source; an input edge belongs to at most one entry, so d_edge is an
+    indexed store into zeros"""
+    ds = _raw_row_softmax_bwd(g, alpha, dalpha)
+    rows, cols = g.row_ids().long(), g.col.long()
+    pre = a_src[cols] if a_dst is None else a_dst[rows] + a_src[cols]
+    if a_edge is not None and a_edge.size(0):
+        eidc, has = _eid_clamped(g)
+        eidc = eidc.long()
+        ae = a_edge[eidc]
+        pre = pre + (ae if has is None else torch.where(has[:, None], ae, torch.zeros_like(ae)))
+    ds = ds * torch.where(pre > 0, torch.ones_like(pre), torch.full_like(pre, slope))
+    d_dst = d_src = d_edge = None
+    if which & _EA_DST and a_dst is not None:
+        d_dst = torch.zeros_like(a_dst).index_add_(0, rows, ds)
+    if which & _EA_SRC:
+        d_src = torch.zeros_like(a_src).index_add_(0, cols, ds)
+    if which & _EA_EDGE and a_edge is not None:
+        d_edge = torch.zeros_like(a_edge)
+        if a_edge.size(0):
+            if has is None:
+                d_edge[eidc] = ds
+            else:
+                d_edge[eidc[has]] = ds[has]
+    return d_dst, d_src, d_edge
+
+
 class _GatAlpha(torch.autograd.Function):
     """alpha[e, h] = softmax over destination row of leaky_relu(a_dst[row_e, h] + a_src[col_e, h]): one launch for all
     heads, scores never stored (mp_gat_alpha_f32)"""
@@ -657,18 +748,8 @@ class _GatAlpha(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dalpha):
         alpha, ad, asr = ctx.saved_tensors
-        g, L = ctx.g, lib()
-        H = alpha.size(1)
-        dalpha = dalpha.contiguous()
-        ds = torch.empty_like(alpha)
-        with torch.cuda.device(alpha.device):
-            check(L.mp_csr_row_softmax_bwd_f32(ptr(g.rowptr), g.num_nodes, H, ptr(alpha), ptr(dalpha), ptr(ds),
-                                               _stream()), "mp_csr_row_softmax_bwd_f32")
-        rows, cols = g.row_ids().long(), g.col.long()
-        pre = ad[rows] + asr[cols]
-        ds = ds * torch.where(pre > 0, torch.ones_like(pre), torch.full_like(pre, ctx.slope))
-        d_dst = torch.zeros_like(ad).index_add_(0, rows, ds)
-        d_src = torch.zeros_like(asr).index_add_(0, cols, ds)
+        which = (_EA_DST if ctx.needs_input_grad[0] else 0) | (_EA_SRC if ctx.needs_input_grad[1] else 0)
+        d_dst, d_src, _ = _alpha_bwd(ctx.g, alpha, dalpha, ad, asr, None, ctx.slope, which)
         return d_dst, d_src, None, None
 
 
@@ -694,71 +775,12 @@ class _EdgeSoftmax(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dp):
         (p,) = ctx.saved_tensors
-        L = lib()
-        g = ctx.g
-        dp = dp.contiguous()
-        ds = torch.empty_like(p)
-        with torch.cuda.device(p.device):
-            check(L.mp_csr_row_softmax_bwd_f32(ptr(g.rowptr), g.num_nodes, p.size(1), ptr(p), ptr(dp),
-                                               ptr(ds), _stream()), "mp_csr_row_softmax_bwd_f32")
-        return ds, None
+        return _raw_row_softmax_bwd(ctx.g, p, dp), None
 
 
 def edge_softmax(g, s):
     """softmax of the per-entry scores over each destination row, per head; s [nnz, H]"""
     return _EdgeSoftmax.apply(s, g)
-
-
-class _SpmmEdgeValues(torch.autograd.Function):
-    """y[i, slice h] = sum_e a[e,h] V[col_e, slice h], differentiable in a and V"""
-    @staticmethod
-    def forward(ctx, a, V, g, heads):
-        a, V = a.contiguous(), _f32c(V, "V")
-        ctx.g, ctx.heads = g, heads
-        ctx.save_for_backward(a, V)
-        return _raw_spmm_heads(g, a, V, heads)
-
-    @staticmethod
-    def backward(ctx, dy):
-        a, V = ctx.saved_tensors
-        g, heads = ctx.g, ctx.heads
-        dy = dy.contiguous()
-        da = _raw_sddmm_dot(g, dy, V, heads, 1.0)
-        gt = g._transpose_sorted()     # (per-entry values are permuted through gt.pos: also when A^T = A)
-        dV = _raw_spmm_heads(gt, a[gt.pos.long()].contiguous(), dy, heads)
-        return da, dV, None, None
-
-
-def _raw_spmm_heads_reduce(g, a, V, heads, reduce):
-    """y[i, slice h] = mean / max over the entries e of row i of a[e,h] V[col_e, slice h] -> (y, argmax [N, d] int32 for
-    max, else None).  One launch of the plan kernel for all heads (mp_spmm_csr_heads_reduce_f32); one weight per entry
-    is the weighted plan aggregation itself; other head counts run one launch per head on column slices."""
-    want = reduce == _lib.MAX
-    if heads == 1:
-        return _raw_spmm(g.with_values(a.reshape(-1).contiguous()), V, reduce, want_argmax=want)
-    L = lib()
-    N, d = g.num_nodes, V.size(1)
-    a = a.contiguous()
-    argmax = torch.empty((N, d), dtype=torch.int32, device=V.device) if want else None
-    if heads in (2, 4, 8):
-        y = placement.empty_or_torch((N, d), V.device, reads=(V,))
-        plan, counts, ws, ws_bytes = _plan_ws(g, V.device, d, reduce, False)
-        with torch.cuda.device(V.device):
-            st = L.mp_spmm_csr_heads_reduce_f32(ptr(g.rowptr), ptr(g.col), ptr(a), N, ptr(plan), counts, heads, reduce,
-                                                ptr(V), V.stride(0), ptr(y), y.stride(0), d, ptr(argmax), ptr(ws),
-                                                ws_bytes, _stream())
-        if st == 0:
-            return y, argmax
-        if st != 2:
-            check(st, "mp_spmm_csr_heads_reduce_f32")
-    dh = d // heads
-    y = torch.empty((N, d), dtype=torch.float32, device=V.device)
-    for h in range(heads):
-        cs = slice(h * dh, (h + 1) * dh)
-        _, am = _raw_spmm(g.with_values(a[:, h].contiguous()), V[:, cs], reduce, want_argmax=want, out=y[:, cs])
-        if want:
-            argmax[:, cs] = am
-    return y, argmax
 
 
 def _raw_heads_max_da(g, argmax, dy, V, heads, idx=None):
@@ -786,16 +808,14 @@ def _raw_heads_max_da(g, argmax, dy, V, heads, idx=None):
     return da[:nnz]
 
 
-class _SpmmEdgeValuesReduce(torch.autograd.Function):
-    """y[i, slice h] = mean / max over row i's entries e of a[e,h] V[col_e, slice h], differentiable in a and V.
-    mean: the sum's backward on dy / (row entry count); max: dV scattered through the argmax (float atomics), da as a
-    masked per-entry dot"""
+class _SpmmEdgeValues(torch.autograd.Function):
+    """y[i, slice h] = sum / mean / max over row i's entries e of a[e,h] V[col_e, slice h], differentiable in a and V.
+    sum: da a per-entry dot, dV the aggregation over the transposed pattern; mean: the sum's backward on dy / (row entry
+    count); max: dV scattered through the argmax (float atomics), da as a masked per-entry dot"""
     @staticmethod
     def forward(ctx, a, V, g, heads, reduce):
         # a dense [nnz, H]: the kernels (the dV scatter of max among them) read a[e * H + h], whatever the caller's strides
         a, V = _f32c(a.reshape(g.nnz, heads), "a").contiguous(), _f32c(V, "V")
-        if V.size(1) % heads:
-            raise ValueError(f"V has {V.size(1)} columns, not a multiple of heads = {heads}")
         y, argmax = _raw_spmm_heads_reduce(g, a, V, heads, reduce)
         ctx.g, ctx.heads, ctx.reduce = g, heads, reduce
         ctx.save_for_backward(a, V, argmax)
@@ -808,23 +828,23 @@ class _SpmmEdgeValuesReduce(torch.autograd.Function):
         dy = dy.contiguous()
         need_a, need_v = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         da = dV = None
-        if ctx.reduce == _lib.MEAN:
-            dym = (dy / g.entry_counts().clamp(min=1.0)[:, None]).contiguous()
+        if ctx.reduce == _lib.MAX:
             if need_a:
-                da = _raw_sddmm_dot(g, dym, V, heads, 1.0)
+                da = _raw_heads_max_da(g, argmax, dy, V, heads)
             if need_v:
-                gt = g._transpose_sorted()
-                dV = _raw_spmm_heads(gt, a[gt.pos.long()].contiguous(), dym, heads)
+                dV = torch.zeros_like(V)
+                with torch.cuda.device(V.device):
+                    check(lib().mp_spmm_heads_max_bwd_f32(ptr(g.col), ptr(a), heads, ptr(argmax), g.num_nodes, V.size(1),
+                                                          ptr(dy), dy.stride(0), ptr(dV), dV.stride(0), _stream()),
+                          "mp_spmm_heads_max_bwd_f32")
             return da, dV, None, None, None
+        if ctx.reduce == _lib.MEAN:
+            dy = (dy / g.entry_counts().clamp(min=1.0)[:, None]).contiguous()
         if need_a:
-            da = _raw_heads_max_da(g, argmax, dy, V, heads)
+            da = _raw_sddmm_dot(g, dy, V, heads, 1.0)
         if need_v:
-            L = lib()
-            dV = torch.zeros_like(V)
-            with torch.cuda.device(V.device):
-                check(L.mp_spmm_heads_max_bwd_f32(ptr(g.col), ptr(a), heads, ptr(argmax), g.num_nodes, V.size(1),
-                                                  ptr(dy), dy.stride(0), ptr(dV), dV.stride(0), _stream()),
-                      "mp_spmm_heads_max_bwd_f32")
+            gt = g._transpose_sorted()     # (per-entry values are permuted through gt.pos: also when A^T = A)
+            dV = _raw_spmm_heads(gt, a[gt.pos.long()].contiguous(), dy, heads)
         return da, dV, None, None, None
 
 
@@ -833,10 +853,7 @@ def spmm_edge_values(g, a, V, heads=1, reduce="sum"):
     reduce: "sum" (or "add"), "mean", "max" (argmax ties: the first entry in CSR order)"""
     if reduce not in _lib.REDUCE:
         raise ValueError(f"reduce must be one of {sorted(_lib.REDUCE)}, got {reduce!r}")
-    r = _lib.REDUCE[reduce]
-    if r == _lib.SUM:
-        return _SpmmEdgeValues.apply(a, V, g, int(heads))
-    return _SpmmEdgeValuesReduce.apply(a, V, g, int(heads), r)
+    return _SpmmEdgeValues.apply(a, V, g, int(heads), _lib.REDUCE[reduce])
 
 
 # =========================================================================================
@@ -1404,13 +1421,33 @@ def agg_dense_id(g, x, W, W_id, id_index, bias=None, relu=False, self_scale=0.0)
 
 
 # ---- two-gather aggregation: messages with an edge feature (generalconv.py:203-209) ---------------------------------
-def _edge_f32(t, name):
-    """an operand of spmm_edge: float32 only, rows unit-stride"""
+_EDGE_KEYS = "keys generaledgeconv and generalsampleedgeconv"
+_EDGE_ATT_KEYS = "attention keys generaledgeattconvv1 and generaledgeattconvv2"
+
+
+def _edge_f32(t, name, op, keys):
+    """an operand of `op`, one of the operators with an edge feature (`keys`: the layer keys it serves, for the
+    message): float32 only, rows unit-stride"""
     _require_hip(t, name)
     if t.dtype != torch.float32:
-        raise TypeError(f"spmm_edge is float32 only: {name} is {t.dtype} (the edge-feature keys generaledgeconv and "
-                        "generalsampleedgeconv have no bfloat16 or float16 form)")
+        raise TypeError(f"{op} is float32 only: {name} is {t.dtype} (the edge-feature {keys} have no bfloat16 or "
+                        "float16 form)")
     return t if t.dim() == 2 and t.stride(1) == 1 else t.contiguous()
+
+
+def _edge_operands(g, op, keys, x, m, t, bias):
+    """x, m, t, bias of spmm_edge / spmm_edge_heads, checked against g and each other: float32, x one row per column of
+    the operator, m as wide as x, t [N, d]; rows unit-stride, bias contiguous"""
+    x, m = _edge_f32(x, "x", op, keys), _edge_f32(m, "m", op, keys)
+    t = None if t is None else _edge_f32(t, "t", op, keys)
+    if x.size(0) != g.num_cols or m.size(1) != x.size(1):
+        raise ValueError(f"x is {tuple(x.shape)}, m is {tuple(m.shape)}: the operator has {g.num_cols} columns and both "
+                         "operands share one width")
+    if t is not None and tuple(t.shape) != (g.num_nodes, x.size(1)):
+        raise ValueError(f"t is {tuple(t.shape)}, expected {(g.num_nodes, x.size(1))}")
+    if bias is not None and bias.dtype != torch.float32:
+        raise TypeError(f"{op} is float32 only: bias is {bias.dtype}")
+    return x, m, t, None if bias is None else bias.contiguous()
 
 
 def _eid_checked(g, n_edges):
@@ -1450,16 +1487,8 @@ def _raw_spmm_edge(g, x, m, t=None, bias=None, reduce=_lib.SUM, want_argmax=Fals
 def _op_spmm_edge_raw(x: Tensor, m: Tensor, t: Optional[Tensor], bias: Optional[Tensor], graph: int, reduce: int,
                       want_argmax: bool) -> Tuple[Tensor, Tensor]:
     g = from_handle(graph)
-    x, m = _edge_f32(x, "x"), _edge_f32(m, "m")
-    t = None if t is None else _edge_f32(t, "t")
-    if x.size(0) != g.num_cols or m.size(1) != x.size(1):
-        raise ValueError(f"x is {tuple(x.shape)}, m is {tuple(m.shape)}: the operator has {g.num_cols} columns and both "
-                         "operands share one width")
-    if t is not None and tuple(t.shape) != (g.num_nodes, x.size(1)):
-        raise ValueError(f"t is {tuple(t.shape)}, expected {(g.num_nodes, x.size(1))}")
-    if bias is not None and bias.dtype != torch.float32:
-        raise TypeError(f"spmm_edge is float32 only: bias is {bias.dtype}")
-    y, argmax = _raw_spmm_edge(g, x, m, t, None if bias is None else bias.contiguous(), reduce, want_argmax)
+    x, m, t, bias = _edge_operands(g, "spmm_edge", _EDGE_KEYS, x, m, t, bias)
+    y, argmax = _raw_spmm_edge(g, x, m, t, bias, reduce, want_argmax)
     return y, (argmax if argmax is not None else _empty_like_none(x, torch.int32))
 
 
@@ -1566,24 +1595,12 @@ def spmm_edge(g, x, m, reduce="sum", t=None, bias=None):
         raise ValueError(f"reduce must be one of {sorted(_lib.REDUCE)}, got {reduce!r}")
     for name, v in (("x", x), ("m", m), ("t", t), ("bias", bias)):
         if v is not None:
-            _require_hip(v, name)
-            if v.dtype != torch.float32:
-                raise TypeError(f"spmm_edge is float32 only: {name} is {v.dtype} (the edge-feature keys generaledgeconv "
-                                "and generalsampleedgeconv have no bfloat16 or float16 form)")
+            _edge_f32(v, name, "spmm_edge", _EDGE_KEYS)
     _eid_checked(g, m.size(0))
     return torch.ops.mp.spmm_edge(x, m, t, bias, g.handle, _lib.REDUCE[reduce])[0]
 
 
 # ---- attention over messages with an edge feature (attconv.py:342-360) ----------------------------------------------
-def _edge_att_f32(t, name, op):
-    """an operand of edge_att_alpha / spmm_edge_heads: float32 only, rows unit-stride"""
-    _require_hip(t, name)
-    if t.dtype != torch.float32:
-        raise TypeError(f"{op} is float32 only: {name} is {t.dtype} (the edge-feature attention keys "
-                        "generaledgeattconvv1 and generaledgeattconvv2 have no bfloat16 or float16 form)")
-    return t if t.dim() == 2 and t.stride(1) == 1 else t.contiguous()
-
-
 def _eid_clamped(g):
     """g.eid with the inserted loops (eid < 0) pointed at row 0, and the mask of the entries that have an input edge (None:
     all of them); cached on g"""
@@ -1601,9 +1618,10 @@ def _eid_clamped(g):
 @custom_op("mp::edge_att_alpha", mutates_args=(), device_types="cuda")
 def _op_edge_att_alpha(a_dst: Optional[Tensor], a_src: Tensor, a_edge: Tensor, graph: int, slope: float) -> Tensor:
     g = from_handle(graph)
-    asr = _edge_att_f32(a_src, "a_src", "edge_att_alpha").contiguous()
-    aed = _edge_att_f32(a_edge, "a_edge", "edge_att_alpha").contiguous()
-    ad = None if a_dst is None else _edge_att_f32(a_dst, "a_dst", "edge_att_alpha").contiguous()
+    op = "edge_att_alpha"
+    asr = _edge_f32(a_src, "a_src", op, _EDGE_ATT_KEYS).contiguous()
+    aed = _edge_f32(a_edge, "a_edge", op, _EDGE_ATT_KEYS).contiguous()
+    ad = None if a_dst is None else _edge_f32(a_dst, "a_dst", op, _EDGE_ATT_KEYS).contiguous()
     H = asr.size(1)
     if asr.size(0) != g.num_cols or aed.size(1) != H or (ad is not None and tuple(ad.shape) != (g.num_nodes, H)):
         raise ValueError(f"a_src is {tuple(asr.shape)}, a_edge {tuple(aed.shape)}, a_dst "
@@ -1624,45 +1642,13 @@ def _(a_dst, a_src, a_edge, graph, slope):
     return a_src.new_empty((from_handle(graph).nnz, a_src.size(1)))
 
 
-_EA_DST, _EA_SRC, _EA_EDGE = 1, 2, 4
-
-
 @custom_op("mp::edge_att_alpha_bwd_raw", mutates_args=(), device_types="cuda")
 def _op_edge_att_alpha_bwd_raw(dalpha: Tensor, alpha: Tensor, a_dst: Optional[Tensor], a_src: Tensor, a_edge: Tensor,
                                graph: int, slope: float, want: int) -> Tuple[Tensor, Tensor, Tensor]:
-    """(d_dst, d_src, d_edge) of edge_att_alpha, each computed when its bit of `want` (1, 2, 4) is set and empty
-    otherwise: the row softmax backward (mp_csr_row_softmax_bwd_f32), the slope mask on the recomputed pre-activation,
-    sums by destination and by source; an input edge belongs to at most one entry, so d_edge is an indexed store into
-    zeros"""
-    g = from_handle(graph)
-    H = alpha.size(1)
-    alpha, dalpha = alpha.contiguous(), dalpha.contiguous()
-    ds = torch.empty_like(alpha)
-    if g.nnz:
-        with torch.cuda.device(alpha.device):
-            check(lib().mp_csr_row_softmax_bwd_f32(ptr(g.rowptr), g.num_nodes, H, ptr(alpha), ptr(dalpha), ptr(ds),
-                                                   _stream()), "mp_csr_row_softmax_bwd_f32")
-    rows, cols = g.row_ids().long(), g.col.long()
-    eidc, has = _eid_clamped(g)
-    eidc = eidc.long()
-    pre = a_src[cols] if a_dst is None else a_dst[rows] + a_src[cols]
-    if a_edge.size(0):
-        ae = a_edge[eidc]
-        pre = pre + (ae if has is None else torch.where(has[:, None], ae, torch.zeros_like(ae)))
-    ds = ds * torch.where(pre > 0, torch.ones_like(pre), torch.full_like(pre, slope))
-    d_dst, d_src, d_edge = (_empty_like_none(alpha) for _ in range(3))     # (returns of a custom op may not alias)
-    if want & _EA_DST and a_dst is not None:
-        d_dst = torch.zeros_like(a_dst).index_add_(0, rows, ds)
-    if want & _EA_SRC:
-        d_src = torch.zeros_like(a_src).index_add_(0, cols, ds)
-    if want & _EA_EDGE:
-        d_edge = torch.zeros_like(a_edge)
-        if a_edge.size(0):
-            if has is None:
-                d_edge[eidc] = ds
-            else:
-                d_edge[eidc[has]] = ds[has]
-    return d_dst, d_src, d_edge
+    """(d_dst, d_src, d_edge) of edge_att_alpha (_alpha_bwd), each computed when its bit of `want` (1, 2, 4) is set and
+    empty otherwise"""
+    grads = _alpha_bwd(from_handle(graph), alpha, dalpha, a_dst, a_src, a_edge, slope, want)
+    return tuple(_empty_like_none(alpha) if d is None else d for d in grads)     # (returns of a custom op may not alias)
 
 
 @_op_edge_att_alpha_bwd_raw.register_fake
@@ -1704,53 +1690,9 @@ def edge_att_alpha(g, a_dst, a_src, a_edge, slope=0.2):
     all three."""
     for name, v in (("a_dst", a_dst), ("a_src", a_src), ("a_edge", a_edge)):
         if v is not None:
-            _edge_att_f32(v, name, "edge_att_alpha")
+            _edge_f32(v, name, "edge_att_alpha", _EDGE_ATT_KEYS)
     _eid_checked(g, a_edge.size(0))
     return torch.ops.mp.edge_att_alpha(a_dst, a_src, a_edge, g.handle, float(slope))
-
-
-SPMM_EDGE_HEADS_ONE_LAUNCH = (2, 4, 8)     # head counts of mp_spmm_csr_edge_heads_f32 beside 1
-
-
-def _raw_spmm_edge_heads(g, w, x, m, t=None, bias=None, heads=1, reduce=_lib.SUM, want_argmax=False, one_launch=True):
-    """y[r, slice h] = reduce_e w[e, h] (x[col_e] + m[eid_e] + t[r])[slice h] + bias -> (y, argmax [N, d] int32 or None):
-    mp_spmm_csr_edge_f32 with val = w for one head, mp_spmm_csr_edge_heads_f32 for 2, 4 or 8 heads at once, and for
-    every other head count one launch of mp_spmm_csr_edge_f32 per head on column slices.  one_launch=False sends 2, 4 and
-    8 heads through the per-head form too (tests, tests/perf/bench_edgeatt.py): the same terms in the same order, the
-    same bits, and the slower form as this function runs it — by 1.5 % on 2e7 entries, where the copies of w's columns cost more
-    than the H launches save, and threefold on 2e5 entries.  The entry values of g take no part: they
-    belong in w."""
-    L = lib()
-    N, d = g.num_nodes, x.size(1)
-    eid = _eid_checked(g, m.size(0))
-    g.plan()                                     # built once, shared by the per-head graphs below
-    if heads == 1:
-        return _raw_spmm_edge(g.with_values(w.reshape(-1)), x, m, t, bias, reduce, want_argmax)
-    if m.size(0) == 0:
-        m = torch.zeros((1, d), dtype=torch.float32, device=x.device)
-    y = placement.empty_or_torch((N, d), x.device, reads=(x, m))
-    argmax = torch.empty((N, d), dtype=torch.int32, device=x.device) if want_argmax else None
-    if one_launch and heads in SPMM_EDGE_HEADS_ONE_LAUNCH:
-        plan, counts, ws, ws_bytes = _plan_ws(g, x.device, d, reduce, False)
-        with torch.cuda.device(x.device):
-            st = L.mp_spmm_csr_edge_heads_f32(ptr(g.rowptr), ptr(g.col), ptr(eid), ptr(w), N, ptr(plan), counts, heads,
-                                              ptr(x), x.stride(0), ptr(m), m.stride(0), ptr(t),
-                                              t.stride(0) if t is not None else 0, ptr(y), y.stride(0), d, reduce,
-                                              ptr(bias), ptr(argmax), ptr(ws), ws_bytes, _stream())
-        if st != 2:
-            check(st, "mp_spmm_csr_edge_heads_f32")
-            return y, argmax
-    dh = d // heads
-    top = g.__dict__.get("_eid_max")
-    for h in range(heads):
-        cs = slice(h * dh, (h + 1) * dh)
-        gh = g.with_values(w[:, h].contiguous())
-        gh.__dict__["_eid_max"] = top            # (checked on g above: no second read of it per head)
-        _, am = _raw_spmm_edge(gh, x[:, cs], m[:, cs], None if t is None else t[:, cs],
-                               None if bias is None else bias[cs], reduce, want_argmax, out=y[:, cs])
-        if want_argmax:
-            argmax[:, cs] = am
-    return y, argmax
 
 
 @custom_op("mp::spmm_edge_heads", mutates_args=(), device_types="cuda")
@@ -1758,21 +1700,12 @@ def _op_spmm_edge_heads(w: Tensor, x: Tensor, m: Tensor, t: Optional[Tensor], bi
                         heads: int, reduce: int) -> Tuple[Tensor, Tensor]:
     g = from_handle(graph)
     op = "spmm_edge_heads"
-    x, m = _edge_att_f32(x, "x", op), _edge_att_f32(m, "m", op)
-    t = None if t is None else _edge_att_f32(t, "t", op)
     if heads < 1 or x.size(1) % heads:
         raise ValueError(f"x has {x.size(1)} columns, not a multiple of heads = {heads}")
+    x, m, t, bias = _edge_operands(g, op, _EDGE_ATT_KEYS, x, m, t, bias)
     # w dense [nnz, H]: the kernels read w[e * H + h], whatever the caller's strides
-    w = _edge_att_f32(w.reshape(g.nnz, heads), "w", op).contiguous()
-    if x.size(0) != g.num_cols or m.size(1) != x.size(1):
-        raise ValueError(f"x is {tuple(x.shape)}, m is {tuple(m.shape)}: the operator has {g.num_cols} columns and both "
-                         "operands share one width")
-    if t is not None and tuple(t.shape) != (g.num_nodes, x.size(1)):
-        raise ValueError(f"t is {tuple(t.shape)}, expected {(g.num_nodes, x.size(1))}")
-    if bias is not None and bias.dtype != torch.float32:
-        raise TypeError(f"spmm_edge_heads is float32 only: bias is {bias.dtype}")
-    y, argmax = _raw_spmm_edge_heads(g, w, x, m, t, None if bias is None else bias.contiguous(), heads, reduce,
-                                     reduce == _lib.MAX)
+    w = _edge_f32(w.reshape(g.nnz, heads), "w", op, _EDGE_ATT_KEYS).contiguous()
+    y, argmax = _raw_spmm_edge_heads(g, w, x, m, t, bias, heads, reduce, reduce == _lib.MAX)
     return y, (argmax if argmax is not None else _empty_like_none(x, torch.int32))
 
 
@@ -1794,8 +1727,8 @@ def _op_spmm_edge_heads_bwd_raw(dy: Tensor, w: Tensor, x: Tensor, m: Tensor, t: 
     L = lib()
     op = "spmm_edge_heads"
     dy = dy if (dy.dim() == 2 and dy.stride(1) == 1) else dy.contiguous()
-    x, m = _edge_att_f32(x, "x", op), _edge_att_f32(m, "m", op)
-    t = None if t is None else _edge_att_f32(t, "t", op)
+    x, m = _edge_f32(x, "x", op, _EDGE_ATT_KEYS), _edge_f32(m, "m", op, _EDGE_ATT_KEYS)
+    t = None if t is None else _edge_f32(t, "t", op, _EDGE_ATT_KEYS)
     w = w.reshape(g.nnz, heads).contiguous()
     N, d = dy.shape
     hw = d // heads
@@ -1901,7 +1834,7 @@ def spmm_edge_heads(g, w, x, m, t=None, heads=1, reduce="sum", bias=None):
         raise ValueError(f"reduce must be one of {sorted(_lib.REDUCE)}, got {reduce!r}")
     for name, v in (("w", w), ("x", x), ("m", m), ("t", t), ("bias", bias)):
         if v is not None:
-            _edge_att_f32(v, name, "spmm_edge_heads")
+            _edge_f32(v, name, "spmm_edge_heads", _EDGE_ATT_KEYS)
     if int(heads) < 1 or x.size(1) % int(heads):
         raise ValueError(f"x has {x.size(1)} columns, not a multiple of heads = {heads}")
     _eid_checked(g, m.size(0))

@@ -549,24 +549,10 @@ int mp_csr_row_softmax_f32(const int32_t* rowptr, int64_t N, int32_t heads,
 int mp_csr_row_softmax_bwd_f32(const int32_t* rowptr, int64_t N, int32_t heads,
                                const float* p, const float* dp, float* ds,
                                mp_stream_t stream);
-/* per-entry dot: g[e*H+h] = <A[row, slice h], B[col, slice h]> — gradient of an
- * aggregation w.r.t. its edge values (A = dY, B = X) */
-int mp_sddmm_grad_f32(const int32_t* rowptr, const int32_t* col, int64_t N, int64_t nnz,
-                      const float* A, int64_t lda, const float* B, int64_t ldb,
-                      int32_t d, int32_t heads, float* g, mp_stream_t stream);
 /* multi-head weighted aggregation on the segment plan — ALL heads in one launch of the hot kernel (full-row loads; a lane
- * applies the weight of the head its columns belong to): Y[r, slice h] = sum_e a[e*H+h] * V[col[e], slice h]
- * (TfgIDLayer.py:340-355 with split_value_heads; idconv.py:317-332).  heads in {1, 2, 4, 8}, d % heads == 0
- * (MP_ERR_UNSUPPORTED otherwise: use mp_spmm_heads_f32).  Workspace as mp_spmm_csr_f32 (mp_spmm_ws_bytes, reduce SUM). */
-int mp_spmm_csr_heads_f32(const int32_t* rowptr, const int32_t* col, const float* a, int64_t N, const int32_t* plan,
-                          const int32_t* counts_host, int32_t heads, const float* V, int64_t ldv, float* Y, int64_t ldy,
-                          int32_t d, void* ws, size_t ws_bytes, mp_stream_t stream);
-/* the same without a plan (one wave per row; any head count): fallback for head layouts the plan kernel does not take */
-int mp_spmm_heads_f32(const int32_t* rowptr, const int32_t* col, const float* a,
-                      int64_t N, int32_t heads, const float* V, int64_t ldv,
-                      float* Y, int64_t ldy, int32_t d, mp_stream_t stream);
-/* mp_spmm_csr_heads_f32 with a reduction: reduce MP_SUM, MP_MEAN or MP_MAX of the weighted messages
- * a[e*H+h] * V[col[e], slice h] over each row's entries — the attention layers' propagate with aggr = cfg.gnn.agg
+ * applies the weight of the head its columns belong to): Y[r, slice h] = reduce_e a[e*H+h] * V[col[e], slice h] with
+ * reduce MP_SUM, MP_MEAN or MP_MAX over each row's entries — the attention sum (TfgIDLayer.py:340-355 with
+ * split_value_heads; idconv.py:317-332) and the attention layers' propagate with aggr = cfg.gnn.agg
  * (graphgym/contrib/layer/attconv.py:93-104 add attention, :196-205 mul attention).  The semantics of
  * mp_spmm_csr_f32: mean divides by the row's entry count, an empty row gives 0, max keeps the first entry in CSR
  * order among equal candidates and writes its index to argmax [N, d] (row stride d; NULL: not written; -1 where no

@@ -6,7 +6,7 @@ bench graph (graphgen BA, 10^7 nodes, self loops: ~1.1e8 entries), d = 256, H in
   bwd_sum / bwd_mean               da (entry-balanced per-entry dot) + dV (aggregation over the transpose)
   max_da                           the masked per-entry dot (mp_spmm_heads_max_da_f32)
   max_dv                           the argmax scatter of dV (mp_spmm_heads_max_bwd_f32; dV zeroing not included)
-  sddmm_grad / sddmm_stream        the unmasked per-entry dot: mp_sddmm_grad_f32 and the entry-balanced kernel
+  sddmm_grad / sddmm_stream        the unmasked per-entry dot: mp_sddmm_dot_f32 (scale 1) and the entry-balanced kernel
 
     NODES=10000000 HEADS=1,4,8 python scripts/att_agg_ab.py OUT.jsonl"""
 import json, os, statistics, sys
@@ -72,8 +72,8 @@ for H in HEADS:
         del dym
         rec["max_da"] = times_of(lambda: ops._raw_heads_max_da(g, argmax, dy, V, H))
         s = torch.empty((g.nnz, H), device=dev)
-        rec["sddmm_grad"] = times_of(lambda: check(L.mp_sddmm_grad_f32(
-            ptr(g.rowptr), ptr(g.col), n, g.nnz, ptr(dy), d, ptr(V), d, d, H, ptr(s), _stream())))
+        rec["sddmm_grad"] = times_of(lambda: check(L.mp_sddmm_dot_f32(
+            ptr(g.rowptr), ptr(g.col), n, g.nnz, ptr(dy), d, ptr(V), d, d, H, 1.0, ptr(s), _stream())))
         rec["sddmm_stream"] = times_of(lambda: ops._raw_sddmm_dot(g, dy, V, H, 1.0))
         dV = torch.zeros_like(V)
         rec["max_dv"] = times_of(lambda: check(L.mp_spmm_heads_max_bwd_f32(

@@ -473,13 +473,9 @@ def test_multi_head_aggregation(dev, wg, lay):
         am2 = torch.empty((n, d), dtype=torch.int32, device=dev) if reduce == "max" else None
         L = _lib.lib()
         with Kept((Vb, Vv, lay)):
-            if reduce == "sum":
-                check(L.mp_spmm_csr_heads_f32(ptr(G.rowptr), ptr(G.col), ptr(ad), n, ptr(plan), counts, heads, ptr(Vv),
-                                              Vv.stride(0), ptr(ov), ov.stride(0), d, ptr(ws), nb, _stream()), what)
-            else:
-                check(L.mp_spmm_csr_heads_reduce_f32(ptr(G.rowptr), ptr(G.col), ptr(ad), n, ptr(plan), counts, heads, red,
-                                                     ptr(Vv), Vv.stride(0), ptr(ov), ov.stride(0), d, ptr(am2), ptr(ws), nb,
-                                                     _stream()), what)
+            check(L.mp_spmm_csr_heads_reduce_f32(ptr(G.rowptr), ptr(G.col), ptr(ad), n, ptr(plan), counts, heads, red,
+                                                 ptr(Vv), Vv.stride(0), ptr(ov), ov.stride(0), d, ptr(am2), ptr(ws), nb,
+                                                 _stream()), what)
         assert_beside(ob, lay, d, what)
         assert same_bits(ov, y), what
         assert am2 is None or torch.equal(am2, am), what
@@ -542,7 +538,7 @@ def test_max_backward(dev, wg, lay):
 @pytest.mark.parametrize("lay", WIDE, ids=IDS)
 @pytest.mark.parametrize("heads,d", [(1, 128), (4, 128), (4, 24)], ids=["stream-1x128", "stream-4x32", "rows-4x6"])
 def test_sddmm(dev, wg, lay, heads, d):
-    """sddmm_dot (the entry-balanced kernel; the row kernel for the head layout 4 x 6), mp_sddmm_grad_f32, and the
+    """sddmm_dot (the entry-balanced kernel; the row kernel for the head layout 4 x 6), mp_sddmm_dot_f32 at scale 1, and the
     gradients of sddmm_dot into Q and K; node operands as wide slices, the per-entry arrays natural"""
     n, G, sub, subT = N_WIDE, wg.G, wg.sub, wg.subT
     dh = d // heads
@@ -564,8 +560,8 @@ def test_sddmm(dev, wg, lay, heads, d):
         s = ops.sddmm_dot(G, Ag, Bg, heads, 0.5)
         s.backward(ds.to(dev))
         g = torch.empty(G.nnz * heads, device=dev)
-        check(_lib.lib().mp_sddmm_grad_f32(ptr(G.rowptr), ptr(G.col), n, G.nnz, ptr(Av), Av.stride(0), ptr(Bv),
-                                           Bv.stride(0), d, heads, ptr(g), _stream()), what)
+        check(_lib.lib().mp_sddmm_dot_f32(ptr(G.rowptr), ptr(G.col), n, G.nnz, ptr(Av), Av.stride(0), ptr(Bv),
+                                          Bv.stride(0), d, heads, 1.0, ptr(g), _stream()), what)
     got = s.detach()[ed].cpu()
     finite(got, what)
     close(got, both(lambda c: ref(c, 0.5)), what=what, mag=both(lambda c: ref(c, 0.5, True))[0])
@@ -585,8 +581,8 @@ def test_sddmm(dev, wg, lay, heads, d):
         assert same_bits(s.detach(), s0.detach()), what
         assert same_bits(Ag.grad, A0.grad) and same_bits(Bg.grad, B0.grad), what      # aggregations in entry order
         g0 = torch.empty_like(g)
-        check(_lib.lib().mp_sddmm_grad_f32(ptr(G.rowptr), ptr(G.col), n, G.nnz, ptr(A0), d, ptr(B0), d, d, heads, ptr(g0),
-                                           _stream()), what)
+        check(_lib.lib().mp_sddmm_dot_f32(ptr(G.rowptr), ptr(G.col), n, G.nnz, ptr(A0), d, ptr(B0), d, d, heads, 1.0,
+                                          ptr(g0), _stream()), what)
         assert same_bits(g, g0), what
 
 

@@ -768,7 +768,7 @@ def test_by_source_normalisation_is_bitwise_reproducible(dev):
 @pytest.mark.parametrize("heads,d", [(2, 64), (4, 256), (8, 128), (4, 24)])
 def test_multi_head_aggregation_in_one_launch(dev, heads, d):
     """Y[r, slice h] = sum_e a[e, h] V[col_e, slice h] for all heads in ONE launch of the plan-based kernel
-    (mp_spmm_csr_heads_f32), hub rows included, against float64; and the gradients of spmm_edge_values through it"""
+    (mp_spmm_csr_heads_reduce_f32), hub rows included, against float64; and the gradients of spmm_edge_values through it"""
     import graphgym_amd as ga
     from graphgym_amd import ops
     g = torch.Generator().manual_seed(heads * 100 + d)
