@@ -92,6 +92,11 @@ PROTOTYPES = {
     "mp_softmax_ce_bwd_f32": (C.c_int, [_p, _i64, _i64, _p, _p, _i64, _i32, _p, _f32, _p, _i64, _p]),
     "mp_rows_gather_f32": (C.c_int, [_p, _i64, _p, _i64, _i32, _p, _i64, _p]),
     "mp_rows_scatter_add_f32": (C.c_int, [_p, _i64, _p, _i64, _i32, _p, _i64, _p]),
+    "mp_embed_sum_f32": (C.c_int, [_p, _i32, _p, _p, _i64, _i64, _i32, _p, _i64, _p]),
+    "mp_code_reduce_max_codes": (C.c_int, []),
+    "mp_code_reduce_ws_bytes": (C.c_int, [_i64, _i32, _i32, _pi32, _psz]),
+    "mp_code_reduce_f32": (C.c_int, [_p, _p, _i32, _p, _p, C.c_int, _p, _p, _i64, _i64, _i32, _p, _i64, _i32, _p, _i64, _p,
+                                     _sz, _p]),
     "mp_sddmm_dot_f32": (C.c_int, [_p, _p, _i64, _i64, _p, _i64, _p, _i64, _i32, _i32, _f32, _p, _p]),
     "mp_sddmm_dot_stream_f32": (C.c_int, [_p, _p, _i64, _p, _i64, _p, _i64, _i32, _i32, _f32, _p, _p]),
     "mp_sddmm_add_f32": (C.c_int, [_p, _p, _i64, _i64, _p, _p, _f32, _p, _p]),

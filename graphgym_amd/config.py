@@ -16,7 +16,10 @@ def _defaults():
                                         edge_dim=128,                    # config.py:145
                                         edge_train_mode="all", edge_message_ratio=0.8,
                                         edge_negative_sampling_ratio=1.0, resample_disjoint=False,
-                                        resample_negative=False)         # config.py:147-163 (link_pred.py)
+                                        resample_negative=False,         # config.py:147-163 (link_pred.py)
+                                        node_encoder=False, node_encoder_name="Atom", node_encoder_bn=True,
+                                        edge_encoder=False, edge_encoder_name="Bond", edge_encoder_bn=True,
+                                        encoder_dim=128)                 # config.py:121-142 (encoders.py)
     cfg.model = types.SimpleNamespace(graph_pooling="add", loss_fun="cross_entropy")      # config.py:285-301
     cfg.train = types.SimpleNamespace(batch_size=16)
     cfg.gnn = types.SimpleNamespace(

@@ -14,7 +14,9 @@ Importing this module is the whole integration:
   * the built-in edge-feature keys 'generaledgeconv', 'generalsampleedgeconv' (graphgym/models/layer.py:233-234),
     installed by install_edge() — a third dictionary, EDGE_KEYS, for the same reason,
   * the edge-feature attention keys 'generaledgeattconvv1', 'generaledgeattconvv2'
-    (graphgym/contrib/layer/attconv.py:542-543), installed by install_edge_att() — a fourth dictionary, EDGE_ATT_KEYS.
+    (graphgym/contrib/layer/attconv.py:542-543), installed by install_edge_att() — a fourth dictionary, EDGE_ATT_KEYS,
+  * the OGB keys 'generalogbconv' (graphgym/contrib/layer/generalconv_ogb.py:141) and 'sageinitconv'
+    (graphgym/contrib/layer/sageinitconv.py:115), installed by install_ogb() — a fifth dictionary, OGB_KEYS.
 
 ``register_layer`` raises KeyError on a duplicate (register.py:6-10), and built-ins shadow
 registered keys (layer.py:238), so taking over an existing key is done by assignment into the
@@ -24,6 +26,7 @@ from . import attconv as A
 from . import edgeattconv as EA
 from . import edgeconv as EC
 from . import layers as L
+from . import ogbconv as OG
 from . import registry as R
 
 ID_KEYS = {
@@ -62,6 +65,10 @@ EDGE_KEYS = {
 EDGE_ATT_KEYS = {
     'generaledgeattconvv1': EA.GeneralEdgeAttConvv1,
     'generaledgeattconvv2': EA.GeneralEdgeAttConvv2,
+}
+OGB_KEYS = {
+    'generalogbconv': OG.GeneralOGBConv,
+    'sageinitconv': OG.SAGEinitConv,
 }
 
 
@@ -114,10 +121,16 @@ def install_edge_att(override=True):
     return _install_keys(EDGE_ATT_KEYS, override)
 
 
+def install_ogb(override=True):
+    """Register the OGB keys of OGB_KEYS with install()'s semantics; returns the keys taken."""
+    return _install_keys(OGB_KEYS, override)
+
+
 installed_keys = install(override=True)
 installed_design_keys = install_design(override=True)
 installed_edge_keys = install_edge(override=True)
 installed_edge_att_keys = install_edge_att(override=True)
+installed_ogb_keys = install_ogb(override=True)
 
 
 # ---- the post-ops of GraphGym's layer wrapper on the engine -------------------------------------------------

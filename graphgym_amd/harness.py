@@ -139,7 +139,7 @@ class GeneralLayer(nn.Module):
         if cfg.gnn.dropout > 0:
             post.append(nn.Dropout(p=cfg.gnn.dropout, inplace=cfg.mem.inplace))
         if has_act and not fuse_relu:
-            post.append(nn.ReLU() if cfg.gnn.act == "relu" else getattr(nn, cfg.gnn.act)())
+            post.append(_act_module())
         self.post_layer = nn.Sequential(*post)
 
     def forward(self, batch):
@@ -235,8 +235,23 @@ class GNNStackStage(nn.Module):
         return batch
 
 
+# graphgym/models/act.py:6-14, built per use (the reference shares one module instance per key)
+act_dict = {
+    'relu': lambda: nn.ReLU(inplace=cfg.mem.inplace),
+    'selu': lambda: nn.SELU(inplace=cfg.mem.inplace),
+    'prelu': lambda: nn.PReLU(),
+    'elu': lambda: nn.ELU(inplace=cfg.mem.inplace),
+    'lrelu_01': lambda: nn.LeakyReLU(negative_slope=0.1, inplace=cfg.mem.inplace),
+    'lrelu_025': lambda: nn.LeakyReLU(negative_slope=0.25, inplace=cfg.mem.inplace),
+    'lrelu_05': lambda: nn.LeakyReLU(negative_slope=0.5, inplace=cfg.mem.inplace),
+}
+
+
 def _act_module():
-    return nn.ReLU() if cfg.gnn.act == "relu" else getattr(nn, cfg.gnn.act)()
+    """cfg.gnn.act through the reference's act_dict keys; a name that is none of them is taken as a torch.nn class, as
+    before"""
+    make = act_dict.get(cfg.gnn.act)
+    return make() if make is not None else getattr(nn, cfg.gnn.act)()
 
 
 def skip_block_forward(block, batch, stage_type, orig=None):
@@ -389,10 +404,36 @@ head_dict = {'node': GNNNodeHead, 'graph': GNNGraphHead,      # head.py:122-127
              'edge': GNNEdgeHead, 'link_pred': GNNEdgeHead}
 
 
+class BatchNorm1dNode(nn.Module):
+    """graphgym/models/layer.py:85-94, the BatchNorm on the engine's passes (same parameters and buffers under `.bn`)"""
+
+    def __init__(self, dim_in):
+        super().__init__()
+        self.bn = mpnn.BatchNorm1d(dim_in, eps=cfg.bn.eps, momentum=cfg.bn.mom)
+
+    def forward(self, batch):
+        batch.node_feature = self.bn(batch.node_feature)
+        return batch
+
+
+class BatchNorm1dEdge(nn.Module):
+    """graphgym/models/layer.py:97-106"""
+
+    def __init__(self, dim_in):
+        super().__init__()
+        self.bn = mpnn.BatchNorm1d(dim_in, eps=cfg.bn.eps, momentum=cfg.bn.mom)
+
+    def forward(self, batch):
+        batch.edge_feature = self.bn(batch.edge_feature)
+        return batch
+
+
 class GNN(nn.Module):
     """graphgym/models/gnn.py:123-168: cfg.gnn.stage_type picks the message-passing stage from stage_dict — 'stack'
     (mp.layer{i}), or 'skipsum' / 'skipconcat' (mp.block{i}.f.{j}: cfg.gnn.skip_every layers per block, the block's last
-    BatchNorm + skip add / concatenation + ReLU as one engine pass); an unknown key raises ValueError.  The feature-augmentation `preprocess` module of the
+    BatchNorm + skip add / concatenation + ReLU as one engine pass); an unknown key raises ValueError.  cfg.dataset.node_encoder /
+    edge_encoder put node_encoder (+ node_encoder_bn) and edge_encoder (+ edge_encoder_bn) ahead of pre_mp and set dim_in
+    to cfg.dataset.encoder_dim (gnn.py:136-150; graphgym_amd.encoders).  The feature-augmentation `preprocess` module of the
     reference holds no parameters and is outside the path: inputs arrive already assembled (the structural features and labels it
     concatenates: graphgym_amd.structure.augment)."""
 
@@ -401,6 +442,18 @@ class GNN(nn.Module):
         stage_type = getattr(cfg.gnn, "stage_type", "stack")
         if stage_type not in stage_dict:
             raise ValueError("cfg.gnn.stage_type must be one of {}, got {!r}".format(sorted(stage_dict), stage_type))
+        ds = cfg.dataset
+        if getattr(ds, "node_encoder", False):       # gnn.py:136-143
+            from .encoders import node_encoder_dict
+            self.node_encoder = node_encoder_dict[ds.node_encoder_name](ds.encoder_dim)
+            if ds.node_encoder_bn:
+                self.node_encoder_bn = BatchNorm1dNode(ds.encoder_dim)
+            dim_in = ds.encoder_dim
+        if getattr(ds, "edge_encoder", False):       # gnn.py:144-149
+            from .encoders import edge_encoder_dict
+            self.edge_encoder = edge_encoder_dict[ds.edge_encoder_name](ds.encoder_dim)
+            if ds.edge_encoder_bn:
+                self.edge_encoder_bn = BatchNorm1dEdge(ds.edge_dim)
         d_in = dim_in
         if cfg.gnn.layers_pre_mp > 0:
             self.pre_mp = GNNPreMP(d_in, cfg.gnn.dim_inner)

@@ -7,6 +7,8 @@ C-ABI entry point of libmpengine.so (include/mp_engine.h).
     edge_softmax / sddmm_*       GAT pieces (TfgIDLayer.py:333-355; idconv.py:317-332)
     spmm_edge(g, x, m, reduce)   aggregation of messages with an edge feature (generalconv.py:203-209)
     edge_att_alpha / spmm_edge_heads   attention over messages with an edge feature (attconv.py:342-360)
+    embed_sum(codes, table, offsets)   rows of stacked embedding tables summed per item (feature_encoder.py:74-81)
+    spmm_code(g, x, table, codes, reduce)   aggregation of messages with a coded edge term (generalconv_ogb.py:115-118)
 """
 import ctypes as C
 import os
@@ -874,8 +876,10 @@ def spmm_edge_values(g, a, V, heads=1, reduce="sum"):
 #   mp::spmm_edge       y = reduce_e w_e (x_j + m_e + t_i) + b         GeneralEdgeConvLayer.message, generalconv.py:203-209
 #   mp::edge_att_alpha  softmax_i lrelu(a_dst_i + a_src_j + a_edge_e)  GeneralEdgeAttConvv1Layer.message, attconv.py:352-357
 #   mp::spmm_edge_heads y = reduce_e w_eh (x_j + m_e + t_i)^h + b      ... attconv.py:358-360
+#   mp::embed_sum       out_r = sum_k table[off_k + codes_rk]          AtomEncoder.forward, feature_encoder.py:74-81
+#   mp::spmm_code       y = reduce_e w_e (x_j + table[q_e]) + b        GeneralOGBConvLayer.message, generalconv_ogb.py:115-118
 # =========================================================================================
-from typing import Optional, Tuple   # noqa: E402
+from typing import List, Optional, Tuple   # noqa: E402
 
 from torch.library import custom_op, register_autograd   # noqa: E402
 
@@ -1464,12 +1468,14 @@ def _eid_checked(g, n_edges):
     return g.eid
 
 
-def _raw_spmm_edge(g, x, m, t=None, bias=None, reduce=_lib.SUM, want_argmax=False, out=None):
+def _raw_spmm_edge(g, x, m, t=None, bias=None, reduce=_lib.SUM, want_argmax=False, out=None, eid=None):
     """one launch of mp_spmm_csr_edge_f32 (+ the hub launches of its plan): y[r] = reduce_e val_e (x[col_e] + m[eid_e] +
-    t[r]) + bias -> (y, argmax [N, d] int32 or None)"""
+    t[r]) + bias -> (y, argmax [N, d] int32 or None).  eid: another per-entry row index into m in the place of g.eid
+    (spmm_code: the entry's code, checked by its caller)"""
     L = lib()
     N, d = g.num_nodes, x.size(1)
-    eid = _eid_checked(g, m.size(0))
+    if eid is None:
+        eid = _eid_checked(g, m.size(0))
     if m.size(0) == 0:      # every entry is an inserted loop: the kernel still reads (and drops) row 0
         m = torch.zeros((1, d), dtype=torch.float32, device=x.device)
     y = out if out is not None else placement.empty_or_torch((N, d), x.device, reads=(x, m))
@@ -1839,3 +1845,302 @@ def spmm_edge_heads(g, w, x, m, t=None, heads=1, reduce="sum", bias=None):
         raise ValueError(f"x has {x.size(1)} columns, not a multiple of heads = {heads}")
     _eid_checked(g, m.size(0))
     return torch.ops.mp.spmm_edge_heads(w, x, m, t, bias, g.handle, int(heads), _lib.REDUCE[reduce])[0]
+
+
+# ---- integer-coded features (feature_encoder.py:13-103) and the coded edge term (generalconv_ogb.py:30-35,115-118) ----
+def code_reduce_cap():
+    """the largest number of table rows mp_code_reduce_f32 takes"""
+    return int(lib().mp_code_reduce_max_codes())
+
+
+def code_reduce_path(n_codes):
+    """'kernel' (mp_code_reduce_f32) or 'operator' (the plan-based aggregation on the transposed one-hot operator) for a
+    table reduction whose items are known ahead of the call (embed_sum's backward; sum and mean of spmm_code).  Above
+    code_reduce_cap() rows only the operator exists.  Below it the choice follows the measurement
+    (profiles/ogb_bench.json): at N = 10^6 the operator took 0.41 ms against the kernel's 1.15 ms for
+    the 60 bond codes and 2.20 ms against 5.45 ms for the 173 atom rows, so the operator is the default; MP_CODE_REDUCE=kernel
+    takes the kernel (it needs no operator build and a workspace of a sixteenth of dY).  The winners of a max
+    aggregation differ per column and have no operator form: they always run on the kernel."""
+    if n_codes > code_reduce_cap():
+        return "operator"
+    return "kernel" if os.environ.get("MP_CODE_REDUCE", "operator") == "kernel" else "operator"
+
+
+_OFFSETS = {}
+
+
+def _offsets_dev(offsets, device):
+    """the K table offsets as an int32 device tensor (one per (offsets, device))"""
+    key = (tuple(int(o) for o in offsets), str(device))
+    t = _OFFSETS.get(key)
+    if t is None:
+        t = _OFFSETS[key] = torch.tensor(key[0], dtype=torch.int32, device=device)
+    return t
+
+
+def _stamp(t):
+    return (t.data_ptr(), tuple(t.shape), t._version)
+
+
+def check_codes(codes, dims, what="codes"):
+    """the int32 copy of integer features [R, K] (K = len(dims)) the kernels read, after checking every column k against
+    [0, dims[k]) — IndexError as nn.Embedding raises.  One device-to-host read: callers cache the result per batch."""
+    if codes.dim() != 2 or codes.size(1) != len(dims) or codes.is_floating_point():
+        raise ValueError(f"{what} must be an integer tensor [R, {len(dims)}], got {codes.dtype} {tuple(codes.shape)}")
+    if codes.size(0):
+        lo, hi = codes.amin(0).cpu().tolist(), codes.amax(0).cpu().tolist()
+        for k, dim in enumerate(dims):
+            if lo[k] < 0 or hi[k] >= dim:
+                raise IndexError(f"{what}[:, {k}] holds {lo[k] if lo[k] < 0 else hi[k]}: index out of range "
+                                 f"[0, {dim})")
+    _require_hip(codes, what)
+    out = codes.to(torch.int32).contiguous()
+    out._mp_checked_dims = tuple(int(v) for v in dims)
+    return out
+
+
+def _raw_embed_sum(codes, table, off, out=None):
+    """one launch of mp_embed_sum_f32 -> out [R, d]"""
+    R, K = codes.shape
+    d = table.size(1)
+    out = torch.empty((R, d), dtype=torch.float32, device=table.device) if out is None else out
+    with torch.cuda.device(table.device):
+        check(lib().mp_embed_sum_f32(ptr(codes), K, ptr(off), ptr(table), table.stride(0), R, d, ptr(out), out.stride(0),
+                                     _stream()), "mp_embed_sum_f32")
+    return out
+
+
+def _raw_code_reduce(dy, codes, n_codes, K=0, off=None, disjoint=False, rowptr=None, rows=None, w=None, sel=None):
+    """one call of mp_code_reduce_f32 -> (dT [n_codes, d], number of partial slabs).  Items of row r: K per row (codes
+    [R, K] + off; disjoint: the K codes of a row lie in K separate tables), the entries rowptr[r] .. rowptr[r+1] (codes,
+    w and rows per entry), or one per column (sel [R, d])"""
+    L = lib()
+    R, d = dy.shape
+    nb, ns = C.c_size_t(0), C.c_int32(0)
+    check(L.mp_code_reduce_ws_bytes(R, n_codes, d, C.byref(ns), C.byref(nb)), "mp_code_reduce_ws_bytes")
+    ws = torch.empty(max(nb.value, 1), dtype=torch.uint8, device=dy.device)
+    dT = torch.empty((n_codes, d), dtype=torch.float32, device=dy.device)
+    with torch.cuda.device(dy.device):
+        check(L.mp_code_reduce_f32(ptr(rowptr), ptr(rows), K, ptr(codes), ptr(off), 1 if disjoint else 0, ptr(w),
+                                   ptr(sel), sel.stride(0) if sel is not None else 0, R, n_codes, ptr(dy),
+                                   dy.stride(0), d, ptr(dT), dT.stride(0), ptr(ws), nb.value, _stream()),
+              "mp_code_reduce_f32")
+    return dT, ns.value
+
+
+_ONEHOT_T = {}     # (stamp of the codes tensor, offsets, n_codes) -> (codes, operator): holding codes keeps its address unique
+
+
+def _code_reduce_fallback(dy, codes, offsets, n_codes):
+    """dTable of embed_sum on the transposed one-hot operator: row (off_k + code) <- item row, one entry per item, summed
+    by the plan kernel — deterministic (a table row with many items takes the hub path).  offsets: the K host integers.
+    The operator is kept per codes tensor (its address, shape and version: a batch's checked codes are one tensor for all
+    steps), for the last few of them."""
+    offsets = tuple(int(o) for o in offsets)
+    key = (_stamp(codes), offsets, int(n_codes))
+    hit = _ONEHOT_T.get(key)
+    if hit is None:
+        if len(_ONEHOT_T) >= 8:
+            _ONEHOT_T.clear()
+        R, K = codes.shape
+        dst = (codes.long() + _offsets_dev(offsets, codes.device).long()[None]).reshape(-1)
+        src = torch.arange(R, device=codes.device).repeat_interleave(K)
+        hit = _ONEHOT_T[key] = (codes, CSRGraph.from_edge_index(torch.stack([src, dst]), n_codes, num_cols=max(R, 1)))
+    return torch.ops.mp.spmm_raw(dy, hit[1].handle, 0, _lib.SUM, None, 0.0, None, False, False)[0]
+
+
+@custom_op("mp::embed_sum", mutates_args=(), device_types="cuda")
+def _op_embed_sum(codes: Tensor, table: Tensor, offsets: List[int]) -> Tensor:
+    table = _edge_f32(table, "table", "embed_sum", "encoders and generalogbconv")
+    return _raw_embed_sum(codes, table, _offsets_dev(offsets, table.device))
+
+
+@_op_embed_sum.register_fake
+def _(codes, table, offsets):
+    return table.new_empty((codes.size(0), table.size(1)))
+
+
+@custom_op("mp::embed_sum_bwd_raw", mutates_args=(), device_types="cuda")
+def _op_embed_sum_bwd_raw(dy: Tensor, codes: Tensor, offsets: List[int], n_codes: int, disjoint: bool) -> Tensor:
+    """dTable [n_codes, d] of embed_sum: the transposed one-hot operator or mp_code_reduce_f32 (code_reduce_path).
+    disjoint: the caller's promise that the K codes of a row lie in K separate tables (embed_sum: codes checked against
+    tables at strictly increasing offsets), which lets K = 3 / 9 update all K accumulators of a row at once"""
+    dy = dy if dy.dim() == 2 and dy.stride(1) == 1 else dy.contiguous()
+    if code_reduce_path(n_codes) == "operator":
+        return _code_reduce_fallback(dy, codes, offsets, n_codes)
+    return _raw_code_reduce(dy, codes, n_codes, K=codes.size(1), off=_offsets_dev(offsets, dy.device),
+                            disjoint=disjoint)[0]
+
+
+@_op_embed_sum_bwd_raw.register_fake
+def _(dy, codes, offsets, n_codes, disjoint):
+    return dy.new_empty((n_codes, dy.size(1)))
+
+
+def _embed_sum_setup(ctx, inputs, output):
+    codes, table, offsets = inputs
+    ctx.n_codes = table.size(0)
+    ctx.offsets = [int(o) for o in offsets]
+    ctx.save_for_backward(codes)
+
+
+def _embed_sum_backward(ctx, dy):
+    (codes,) = ctx.saved_tensors
+    dtable = None
+    if ctx.needs_input_grad[1]:
+        off = ctx.offsets
+        # the forward's contract: every code was checked against its own table, so increasing offsets separate them
+        disjoint = all(a < b for a, b in zip(off, off[1:]))
+        dtable = torch.ops.mp.embed_sum_bwd_raw(dy, codes, off, ctx.n_codes, disjoint)
+    return None, dtable, None
+
+
+register_autograd("mp::embed_sum", _embed_sum_backward, setup_context=_embed_sum_setup)
+
+
+def embed_sum(codes, table, offsets):
+    """out[r] = ((0 + table[off_0 + codes[r, 0]]) + table[off_1 + codes[r, 1]]) + ...   (torch.ops.mp.embed_sum)
+
+    The sum of embedding rows of the reference's encoders (AtomEncoder.forward, feature_encoder.py:74-81) with the K
+    tables stacked into `table` [C, d] (float32, any leading dimension) at the row offsets `offsets`; the additions run
+    in the reference's order, so the bits are those of its fp32 loop.  codes [R, K]: the int32 tensor check_codes
+    returned for these tables is taken as it is; any other integer tensor is checked here (IndexError outside a
+    table).  The gradient flows to table, without float atomics (code_reduce_path: the aggregation on the transposed one-hot
+    operator, or mp_code_reduce_f32 up to code_reduce_cap() rows)."""
+    offsets = [int(o) for o in offsets]
+    dims = tuple(b - a for a, b in zip(offsets, offsets[1:] + [table.size(0)]))
+    if getattr(codes, "_mp_checked_dims", None) != dims or codes.dtype != torch.int32:
+        codes = check_codes(codes, dims)
+    if table.dtype != torch.float32:
+        raise TypeError(f"embed_sum is float32 only: table is {table.dtype}")
+    return torch.ops.mp.embed_sum(codes, table, offsets)
+
+
+def entry_codes(g, codes):
+    """codes [E] int32 per INPUT edge -> per stored entry of g (q of the entry's input edge, -1 for an inserted self
+    loop), with the largest entry code and the smallest input code; cached on g for this codes tensor"""
+    hit = g.__dict__.get("_entry_codes")
+    if hit is None or hit[0] is not codes:
+        eid = g.eid
+        if eid is None:
+            raise ValueError("spmm_code needs a graph that knows the input position of its entries (CSRGraph.eid)")
+        if g.nnz and int(eid.max().item()) >= codes.numel():
+            raise ValueError(f"codes has {codes.numel()} rows, the graph's entries come from input edges up to "
+                             f"{int(eid.max().item())}")
+        q = codes[eid.clamp(min=0).long()] if codes.numel() else torch.full_like(eid, -1)
+        q = torch.where(eid >= 0, q, torch.full_like(q, -1)).to(torch.int32).contiguous()
+        top = int(q.max().item()) if g.nnz else -1
+        low = int(codes.min().item()) if codes.numel() else 0
+        hit = (codes, q, top, low)
+        g.__dict__["_entry_codes"] = hit
+    return hit[1], hit[2], hit[3]
+
+
+@custom_op("mp::spmm_code", mutates_args=(), device_types="cuda")
+def _op_spmm_code(x: Tensor, table: Tensor, bias: Optional[Tensor], qe: Tensor, graph: int,
+                  reduce: int) -> Tuple[Tensor, Tensor]:
+    g = from_handle(graph)
+    x, table, _, bias = _edge_operands(g, "spmm_code", "key generalogbconv", x, table, None, bias)
+    y, argmax = _raw_spmm_edge(g, x, table, None, bias, reduce, reduce == _lib.MAX, eid=qe)
+    return y, (argmax if argmax is not None else _empty_like_none(x, torch.int32))
+
+
+@_op_spmm_code.register_fake
+def _(x, table, bias, qe, graph, reduce):
+    n = from_handle(graph).num_nodes
+    return x.new_empty((n, x.size(1))), x.new_empty((n, x.size(1)) if reduce == _lib.MAX else (0,), dtype=torch.int32)
+
+
+@custom_op("mp::spmm_code_bwd_raw", mutates_args=(), device_types="cuda")
+def _op_spmm_code_bwd_raw(dy: Tensor, argmax: Tensor, qe: Tensor, graph: int, reduce: int, n_codes: int) -> Tensor:
+    """dTable [n_codes, d] of spmm_code (mp_code_reduce_f32): sum / mean over the entries of each row with weights val
+    (/ the row's entry count), max over each column's winning entry"""
+    g = from_handle(graph)
+    dy = dy if dy.dim() == 2 and dy.stride(1) == 1 else dy.contiguous()
+    if reduce == _lib.MAX:
+        return _raw_code_reduce(dy, qe, n_codes, w=g.val, sel=argmax)[0]
+    w = g.val
+    if reduce == _lib.MEAN:        # entry weights val / (entry count of the row), cached on the graph
+        w = g.__dict__.get("_mean_entry_w")
+        if w is None:
+            w = (1.0 / g.entry_counts().clamp(min=1.0))[g.row_ids().long()]
+            w = g.__dict__["_mean_entry_w"] = (w if g.val is None else w * g.val).contiguous()
+    if code_reduce_path(n_codes) == "operator":
+        return _entry_reduce_fallback(dy, g, qe, w, reduce, n_codes)
+    return _raw_code_reduce(dy, qe, n_codes, rowptr=g.rowptr, rows=g.row_ids(), w=w)[0]
+
+
+def _entry_reduce_fallback(dy, g, qe, w, reduce, n_codes):
+    """dTable of spmm_code (sum / mean) on the transposed one-hot operator of the entries: row q_e <- the entry's row,
+    value w_e, entries without a code left out; cached on g (the op's graph handle names it) for this qe by address,
+    shape and version"""
+    cache = g.__dict__.setdefault("_code_onehot_t", {})
+    hit = cache.get((reduce, n_codes))
+    if hit is None or hit[2] != _stamp(qe):
+        keep = torch.nonzero(qe >= 0).view(-1)
+        ei = torch.stack([g.row_ids().long()[keep], qe.long()[keep]])
+        op = CSRGraph.from_edge_index(ei, n_codes, None if w is None else w[keep], num_cols=max(g.num_nodes, 1))
+        hit = cache[(reduce, n_codes)] = (qe, op, _stamp(qe))
+    return torch.ops.mp.spmm_raw(dy, hit[1].handle, 0, _lib.SUM, None, 0.0, None, False, False)[0]
+
+
+@_op_spmm_code_bwd_raw.register_fake
+def _(dy, argmax, qe, graph, reduce, n_codes):
+    return dy.new_empty((n_codes, dy.size(1)))
+
+
+def _spmm_code_setup(ctx, inputs, output):
+    ctx.set_materialize_grads(False)
+    x, table, bias, qe, graph, reduce = inputs
+    ctx.graph, ctx.reduce, ctx.n_codes = graph, reduce, table.size(0)
+    ctx.g_alive = from_handle(graph)
+    ctx.has_bias = bias is not None
+    ctx.save_for_backward(output[1], qe)
+
+
+def _spmm_code_backward(ctx, dy, _dargmax):
+    argmax, qe = ctx.saved_tensors
+    if dy is None:
+        return None, None, None, None, None, None
+    dy = dy.contiguous()
+    need = ctx.needs_input_grad
+    dx = dtable = dbias = None
+    if need[0]:     # the operand gathered by source: the plain aggregation's backward
+        if ctx.reduce == _lib.MAX:
+            dx = torch.ops.mp.spmm_max_bwd_raw(dy, argmax, ctx.graph)
+        else:
+            dx = torch.ops.mp.spmm_raw(dy, ctx.graph, 1 if ctx.reduce == _lib.SUM else 2, _lib.SUM, None, 0.0, None,
+                                       False, False)[0]
+    if need[1]:
+        dtable = torch.ops.mp.spmm_code_bwd_raw(dy, argmax, qe, ctx.graph, ctx.reduce, ctx.n_codes)
+    if ctx.has_bias and need[2]:
+        dbias = dy.sum(0)
+    return dx, dtable, dbias, None, None, None
+
+
+register_autograd("mp::spmm_code", _spmm_code_backward, setup_context=_spmm_code_setup)
+
+
+def spmm_code(g, x, table, codes, reduce="sum", bias=None):
+    """y[i] = reduce_{e = (i <- j)} w_e (x[j] + table[codes[eid_e]]) + bias   (torch.ops.mp.spmm_code)
+
+    spmm_edge whose edge term is a row of a small table chosen by an integer code per INPUT edge (the bond term of
+    GeneralOGBConvLayer.message, generalconv_ogb.py:115-118): codes [E] int32 in [0, table rows), checked once per
+    (graph, codes) pair; an inserted self loop has no table term.  The forward is the two-gather launch with the entry's
+    code in the place of its input position; nothing of size [E, d] exists in either direction.  The gradient flows to
+    x, table and bias; dtable has no float atomics (code_reduce_path: the one-hot operator or mp_code_reduce_f32; 'max'
+    always the kernel), dx of 'max' does (mp_spmm_max_bwd_f32).
+    float32 only; table rows up to code_reduce_cap()."""
+    if reduce not in _lib.REDUCE:
+        raise ValueError(f"reduce must be one of {sorted(_lib.REDUCE)}, got {reduce!r}")
+    for name, v in (("x", x), ("table", table), ("bias", bias)):
+        if v is not None:
+            _edge_f32(v, name, "spmm_code", "key generalogbconv")
+    if codes.dtype != torch.int32 or codes.dim() != 1:
+        raise ValueError(f"codes must be int32 [E], got {codes.dtype} {tuple(codes.shape)}")
+    if table.size(0) > code_reduce_cap():
+        raise ValueError(f"spmm_code takes tables of up to {code_reduce_cap()} rows, got {table.size(0)}")
+    qe, top, low = entry_codes(g, codes)
+    if top >= table.size(0) or low < 0:
+        raise IndexError(f"codes reach {top if top >= table.size(0) else low}: index out of range [0, {table.size(0)})")
+    return torch.ops.mp.spmm_code(x, table, bias, qe, g.handle, _lib.REDUCE[reduce])[0]

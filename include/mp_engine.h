@@ -507,6 +507,41 @@ int mp_rows_scatter_add_f32(float* H, int64_t ldh, const int64_t* idx, int64_t n
                             int32_t d, const float* U, int64_t ldu, mp_stream_t stream);
 
 /* ------------------------------------------------------------------ *
+ * Integer-coded features (graphgym/models/feature_encoder.py:13-103;  *
+ * the bond term of graphgym/contrib/layer/generalconv_ogb.py:30-35)    *
+ * ------------------------------------------------------------------ */
+/* out[r] = ((0 + table[off_0 + codes[r,0]]) + table[off_1 + codes[r,1]]) + ... — AtomEncoder.forward's loop
+ * (feature_encoder.py:74-81) with the K tables stacked into one [C, d] operand; the additions run in that order, so
+ * the result has the bits of the fp32 loop.  codes [R, K] int32 (dense), offsets [K] int32 on the DEVICE (NULL:
+ * zeros), table rows unit-stride with leading dimension ldt >= d, out with ldo >= d.  The CALLER has checked every
+ * code against its table's row count; the kernel does not.  K > 64: MP_ERR_UNSUPPORTED. */
+int mp_embed_sum_f32(const int32_t* codes, int32_t K, const int32_t* offsets, const float* table, int64_t ldt,
+                     int64_t R, int32_t d, float* out, int64_t ldo, mp_stream_t stream);
+/* the largest C mp_code_reduce_f32 takes (208: 52 KiB of LDS per wave, three waves per CU) */
+int mp_code_reduce_max_codes(void);
+/* workspace of mp_code_reduce_f32: n_slabs * C * d floats, n_slabs = clamp(R / (16 C), 1, 1024) (also written to
+ * *n_slabs when not NULL) — at most max(C d, R d / 16) floats.  C above the cap: MP_ERR_UNSUPPORTED. */
+int mp_code_reduce_ws_bytes(int64_t R, int32_t C, int32_t d, int32_t* n_slabs, size_t* bytes);
+/* dT[c, :] = sum over the items i with code_i = c of w_i * dY[row_i, :] — the gradient of mp_embed_sum_f32 into the
+ * table, and of a table term gathered per CSR entry.  Every row of dT [C, d] is WRITTEN (a code no item carries gets
+ * exactly 0).  No float atomics: a wave owns a range of rows and 64 columns, accumulates in lane-private LDS words and
+ * stores one [C, 64] partial; the partials are added in index order.  The grid depends on (R, C, d) only: the same
+ * bits every run.  Items of row r:
+ *   rowptr NULL, sel NULL   K per row: item k has code offsets[k] + codes[r*K + k] and weight w[r*K + k]; K <= 64.
+ *                           tables_disjoint != 0 promises that the K codes of a row differ (K stacked tables, each
+ *                           code inside its own): K = 3 and K = 9 then update all K accumulators at once
+ *   rowptr given            entries rowptr[r] .. rowptr[r+1]: code codes[i] (< 0: no term), weight w[i]; rows [nnz]
+ *                           holds the row of every entry (a mean is the caller's weights w[i] / row count)
+ *   sel given [R, d], lds   one item per row AND column, sel[r*lds + c] (< 0: none): code codes[item], weight w[item]
+ *                           (the argmax of a max aggregation; rowptr must be NULL)
+ * w NULL = ones; offsets on the DEVICE, NULL = zeros.  Codes are the caller's to check; one outside [0, C) adds
+ * nothing.  C > mp_code_reduce_max_codes() or R >= 2^31: MP_ERR_UNSUPPORTED. */
+int mp_code_reduce_f32(const int32_t* rowptr, const int32_t* rows, int32_t K, const int32_t* codes,
+                       const int32_t* offsets, int tables_disjoint, const float* w, const int32_t* sel, int64_t lds,
+                       int64_t R, int32_t C, const float* dY, int64_t ldy, int32_t d, float* dT, int64_t ldt, void* ws,
+                       size_t ws_bytes, mp_stream_t stream);
+
+/* ------------------------------------------------------------------ *
  * Attention pieces (K12, K13) for the GAT layers                      *
  * ------------------------------------------------------------------ */
 /* dot-product scores: s[e*H+h] = scale * <Qm[row, h-th slice], Km[col, h-th slice]>
