@@ -9,6 +9,7 @@ from ._lib import EngineError, LIB_PATH, lib  # noqa: F401
 from .graph import CSRGraph  # noqa: F401
 from . import ops  # noqa: F401
 from . import link_pred  # noqa: F401
+from . import samplers  # noqa: F401
 
 __version__ = "0.1.0"
 

@@ -119,6 +119,14 @@ PROTOTYPES = {
     "mp_hop_distances": (C.c_int, [_p, _p, _i64, _i64, _p, _i64, _i64, _p, _p, _i64, _p, _p, _p, _i64, _p, _p]),
     "mp_pair_space_rows": (C.c_int, [_p, _p, _i64, _i64, _p, _i64, _i32, _p, _p, _p]),
     "mp_sample_non_edges": (C.c_int, [_p, _p, _i64, _i64, _p, _i64, _p, _p, _i64, _i32, C.c_uint64, C.c_uint64, _p, _p]),
+    "mp_sample_parts": (C.c_int, [_i64, _i64, C.c_uint64, C.c_uint64, _p, _p]),
+    "mp_sample_entry_rows": (C.c_int, [_p, _i64, _i64, _i64, C.c_uint64, C.c_uint64, _p, _p]),
+    "mp_sample_walks": (C.c_int, [_p, _p, _i64, _i64, _p, _i64, _i64, _i32, C.c_uint64, C.c_uint64, _p, _p]),
+    "mp_bitmap_mark": (C.c_int, [_p, _i64, _i64, _p, _p, _p]),
+    "mp_bitmap_word_counts": (C.c_int, [_p, _i64, _p, _p]),
+    "mp_bitmap_nodes": (C.c_int, [_p, _p, _i64, _p, _p]),
+    "mp_induced_count": (C.c_int, [_p, _p, _i64, _i64, _p, _i64, _p, _p, _p]),
+    "mp_induced_fill": (C.c_int, [_p, _p, _i64, _i64, _p, _i64, _p, _p, _p, _p, _p, _p]),
     "mp_csr_triangles": (C.c_int, [_p, _p, _p, _i64, _i64, _p, _p, _p]),
     "mp_hop_sums": (C.c_int, [_p, _p, _i64, _i64, _p, _i64, _i64, _p, _p, _i64, _p, _p, _p]),
     "mp_lpt_partition_host":(C.c_int, [_p, _i64, _i32, _p]),

@@ -21,7 +21,10 @@ def _defaults():
                                         edge_encoder=False, edge_encoder_name="Bond", edge_encoder_bn=True,
                                         encoder_dim=128)                 # config.py:121-142 (encoders.py)
     cfg.model = types.SimpleNamespace(graph_pooling="add", loss_fun="cross_entropy")      # config.py:285-301
-    cfg.train = types.SimpleNamespace(batch_size=16)
+    # config.py:212-248 (samplers.py); train.train_parts (read by loader_pyg.py:218) has no default there or here
+    cfg.train = types.SimpleNamespace(batch_size=16, sampler="full_batch", iter_per_epoch=32, walk_length=4,
+                                      neighbor_sizes=[20, 15, 10, 5])
+    cfg.val = types.SimpleNamespace(sampler="full_batch")                 # config.py:254-261
     cfg.gnn = types.SimpleNamespace(
         layers_pre_mp=0, layers_mp=2, layers_post_mp=1, dim_inner=16,
         layer_type="generalconv", stage_type="stack", batchnorm=True, act="relu",

@@ -21,33 +21,17 @@
 //   4. undirected: (r, c), r < c; directed: (c, r) as (src, dst).
 // Sample i of graph g depends on (seed, offset, g, i) and the graph alone, never on the launch geometry.
 #include "common.h"
+#include "draws.h"       // mix64, kGolden, upper_bound
 
 namespace mp {
 
 constexpr int kFeistelRounds = 6;
-constexpr uint64_t kGolden = 0x9E3779B97F4A7C15ull;
-
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {       // (the splitmix64 finaliser)
-  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-  z ^= z >> 27; z *= 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 
 __device__ __forceinline__ uint32_t feistel_round(uint32_t half, uint32_t key) {      // (the murmur3 finaliser)
   uint32_t x = half + key;
   x ^= x >> 16; x *= 0x85EBCA6Bu;
   x ^= x >> 13; x *= 0xC2B2AE35u;
   return x ^ (x >> 16);
-}
-
-// first index in [lo, hi) whose value is above key
-template <class T>
-__device__ __forceinline__ int64_t upper_bound(const T* __restrict__ a, int64_t lo, int64_t hi, int64_t key) {
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if ((int64_t)a[mid] <= key) lo = mid + 1; else hi = mid;
-  }
-  return lo;
 }
 
 // the graph (or the slot range) that holds x: the last g in [0, G) with ptr[g] <= x

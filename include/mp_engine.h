@@ -777,6 +777,49 @@ int mp_sample_non_edges(const int32_t* rowptr, const int32_t* col, int64_t N, in
                         int64_t* out, mp_stream_t stream);
 
 /* ------------------------------------------------------------------ *
+ * Mini-batch subgraph samplers (GraphGym's train.sampler: random_node, *
+ * saint_node, saint_edge, saint_rw; graphgym/loader_pyg.py:204-255):   *
+ * keyed draws of a node set, the set as a bitmap of N bits, and the    *
+ * induced subgraph written in the engine's CSR order from the selected *
+ * rows only.  key(seed, offset, i, t) = four chained splitmix64 steps  *
+ * (csrc/sample.hip states it); a bounded draw is the high 64 bits of   *
+ * key * n.  Draw i depends on (seed, offset, i, t) and the graph       *
+ * alone.  int32 node ids throughout; N or nnz >= 2^31:                 *
+ * MP_ERR_UNSUPPORTED.  Nothing is allocated, no synchronisation.       *
+ * ------------------------------------------------------------------ */
+/* part[v] <- mulhi(key(seed, epoch, v, 0), num_parts) for v in [0, N): the parts of an epoch partition the nodes. */
+int mp_sample_parts(int64_t N, int64_t num_parts, uint64_t seed, uint64_t epoch, int32_t* part, mp_stream_t stream);
+/* out[i] <- the row that holds stored entry mulhi(key(seed, offset, i, 0), nnz), i in [0, K): a node is drawn with
+ * probability proportional to its stored in-degree, with replacement.  K > 0 with nnz == 0: MP_ERR_INVALID_ARG. */
+int mp_sample_entry_rows(const int32_t* rowptr, int64_t N, int64_t nnz, int64_t K, uint64_t seed, uint64_t offset,
+                         int32_t* out, mp_stream_t stream);
+/* K walks of walk_length steps along the rows of the CSR (row u = the nodes u moves to: pass the transpose of a
+ * directed engine CSR to follow out-edges), out [K, walk_length + 1] row-major.  The root of walk i is
+ * pool[mulhi(key(.., i, 0), n_pool)], or mulhi(key(.., i, 0), N) with pool == NULL; step t >= 1 moves to
+ * col[rowptr[cur] + mulhi(key(.., i, t), deg(cur))]; a node with an empty row stays where it is. */
+int mp_sample_walks(const int32_t* rowptr, const int32_t* col, int64_t N, int64_t nnz, const int32_t* pool,
+                    int64_t n_pool, int64_t K, int32_t walk_length, uint64_t seed, uint64_t offset, int32_t* out,
+                    mp_stream_t stream);
+/* bitmap [ceil(N / 32)] uint32 (bit v & 31 of word v >> 5) |= the nodes[0 .. n): an entry below 0 is skipped (no draw),
+ * one at or above N is skipped and sets flags[0] (int32, device).  The caller zeroes bitmap and flags. */
+int mp_bitmap_mark(const int32_t* nodes, int64_t n, int64_t N, uint32_t* bitmap, int32_t* flags, mp_stream_t stream);
+/* counts[w] <- popcount(bitmap[w]).  word_rank [n_words + 1] = 0 followed by the caller's inclusive prefix sum. */
+int mp_bitmap_word_counts(const uint32_t* bitmap, int64_t n_words, int32_t* counts, mp_stream_t stream);
+/* orig [word_rank[n_words]] <- the set bits in ascending order: word w writes from word_rank[w] on. */
+int mp_bitmap_nodes(const uint32_t* bitmap, const int32_t* word_rank, int64_t n_words, int32_t* orig, mp_stream_t stream);
+/* cnt[k] <- the entries of row orig[k] of the base whose column is in the bitmap, k in [0, n_sub).  orig ascending,
+ * every id in [0, N).  A row is walked by 16 lanes in chunks. */
+int mp_induced_count(const int32_t* rowptr, const int32_t* col, int64_t N, int64_t nnz, const int32_t* orig,
+                     int64_t n_sub, const uint32_t* bitmap, int32_t* cnt, mp_stream_t stream);
+/* The induced subgraph's entries: for row k, from rowptr_sub[k] on (rowptr_sub [n_sub + 1] = 0 followed by the inclusive
+ * prefix sum of mp_induced_count's cnt), col_sub <- the new id of every member column, word_rank[c >> 5] +
+ * popcount(bitmap[c >> 5] below bit c & 31), and base_entry <- the entry's position in the base CSR, in stored order:
+ * col_sub ascends inside a row, equal entries keep the base's order, self and repeated entries are kept as stored. */
+int mp_induced_fill(const int32_t* rowptr, const int32_t* col, int64_t N, int64_t nnz, const int32_t* orig,
+                    int64_t n_sub, const uint32_t* bitmap, const int32_t* word_rank, const int32_t* rowptr_sub,
+                    int32_t* col_sub, int32_t* base_entry, mp_stream_t stream);
+
+/* ------------------------------------------------------------------ *
  * Structural labels and features (graphgym/models/feature_augment.py)  *
  * The engine's CSR, columns ascending inside a row.  Integer results:  *
  * bit-reproducible.  Nothing is allocated, no synchronisation.         *
