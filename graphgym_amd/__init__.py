@@ -10,6 +10,7 @@ from .graph import CSRGraph  # noqa: F401
 from . import ops  # noqa: F401
 from . import link_pred  # noqa: F401
 from . import samplers  # noqa: F401
+from . import graph_loader  # noqa: F401
 
 __version__ = "0.1.0"
 

@@ -127,7 +127,11 @@ PROTOTYPES = {
     "mp_bitmap_nodes": (C.c_int, [_p, _p, _i64, _p, _p]),
     "mp_induced_count": (C.c_int, [_p, _p, _i64, _i64, _p, _i64, _p, _p, _p]),
     "mp_induced_fill": (C.c_int, [_p, _p, _i64, _i64, _p, _i64, _p, _p, _p, _p, _p, _p]),
-    "mp_csr_triangles": (C.c_int, [_p, _p, _p, _i64, _i64, _p, _p, _p]),
+    "mp_collate_stage_cap": (C.c_int, []),
+    "mp_collate_graphs": (C.c_int, [_p, _p, _p, _i64, _i64, _p, _i64, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p,
+                                    _p, _p, _p, _p]),
+    "mp_collate_check_entries": (C.c_int, [_p, _p, _i64, _p, _i64, _p, _p]),
+    "mp_csr_triangles":(C.c_int, [_p, _p, _p, _i64, _i64, _p, _p, _p]),
     "mp_hop_sums": (C.c_int, [_p, _p, _i64, _i64, _p, _i64, _i64, _p, _p, _i64, _p, _p, _p]),
     "mp_lpt_partition_host":(C.c_int, [_p, _i64, _i32, _p]),
     "mp_gen_ba_edges_host": (C.c_int, [_i64, _i32, C.c_uint64, _p, _p, _p]),

@@ -358,10 +358,11 @@ class GNNGraphHead(nn.Module):
         self.pooling_fun = pooling_dict[cfg.model.graph_pooling]
 
     def forward(self, batch):
+        operator = getattr(batch, "pool_operator", None)      # a loader batch brings its own (graph_loader.collate)
         if cfg.dataset.transform == 'ego':
-            graph_emb = self.pooling_fun(batch.node_feature, batch.batch, batch.node_id_index)
+            graph_emb = self.pooling_fun(batch.node_feature, batch.batch, batch.node_id_index, operator=operator)
         else:
-            graph_emb = self.pooling_fun(batch.node_feature, batch.batch)
+            graph_emb = self.pooling_fun(batch.node_feature, batch.batch, operator=operator)
         batch.graph_feature = self.layer_post_mp(graph_emb)
         return batch.graph_feature, batch.graph_label
 

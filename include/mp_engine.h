@@ -820,6 +820,37 @@ int mp_induced_fill(const int32_t* rowptr, const int32_t* col, int64_t N, int64_
                     int32_t* col_sub, int32_t* base_entry, mp_stream_t stream);
 
 /* ------------------------------------------------------------------ *
+ * Graph-task batches (GraphGym's dataset.task = graph: the collation   *
+ * of graphgym/loader.py:247-260).  A dataset is one base CSR holding   *
+ * the disjoint union of G graphs, graph g = nodes graph_ptr[g] ..      *
+ * graph_ptr[g+1] (device, int64) and so entries rowptr[graph_ptr[g]]   *
+ * .. rowptr[graph_ptr[g+1]].  int32 node and entry ids; any size at or *
+ * above 2^31 - 1: MP_ERR_UNSUPPORTED.  Nothing is allocated, nothing   *
+ * is read back, no synchronisation.                                    *
+ * ------------------------------------------------------------------ */
+/* The batch of the graphs ids [B] (device int32, batch order, any order, repeats allowed).  node_off / entry_off [B + 1]
+ * (device int32): the exclusive prefix sums of the listed graphs' node and entry counts, computed by the caller from its
+ * host mirrors of graph_ptr and of rowptr[graph_ptr]; n = node_off[B], nnz = entry_off[B].  One thread per output element,
+ * one launch.  Batch node k of batch graph j (node_off[j] <= k < node_off[j+1]) is base node v = graph_ptr[ids[j]] + k -
+ * node_off[j]:  rowptr_out[k] <- rowptr[v] - rowptr[graph_ptr[ids[j]]] + entry_off[j] (rowptr_out[n] <- nnz),
+ * owner[k] <- j (int64) and owner32[k] <- j, orig_node[k] <- v.  Batch entry e of batch graph j is base entry s =
+ * rowptr[graph_ptr[ids[j]]] + e - entry_off[j]:  col_out[e] <- col[s] - graph_ptr[ids[j]] + node_off[j], row_out[e] <-
+ * the batch row that holds e, base_entry[e] <- s, edge_index [2, nnz] (int64, row-major) <- (col_out; row_out), and
+ * val_out[e] <- val[s] when val_out is given (val then must be).  The owner search is an upper bound over the B + 1
+ * offsets, staged in LDS up to mp_collate_stage_cap() offsets, read from global memory above.  B == 0 or n == 0: MP_OK
+ * without a launch; nnz == 0 writes the node arrays only (the entry outputs may be NULL). */
+int mp_collate_stage_cap(void);
+int mp_collate_graphs(const int32_t* rowptr, const int32_t* col, const float* val, int64_t N, int64_t nnz_base,
+                      const int64_t* graph_ptr, int64_t G, const int32_t* ids, const int32_t* node_off,
+                      const int32_t* entry_off, int64_t B, int64_t n, int64_t nnz, int32_t* rowptr_out, int64_t* owner,
+                      int32_t* owner32, int64_t* orig_node, int32_t* col_out, int32_t* row_out, int32_t* base_entry,
+                      int64_t* edge_index, float* val_out, mp_stream_t stream);
+/* first_bad[0] (device int32, set to INT32_MAX by the caller) <- the smallest stored entry whose column lies outside the
+ * graph of its row (row_of from mp_csr_row_ids): an entry that joins two graphs.  nnz == 0: MP_OK without a launch. */
+int mp_collate_check_entries(const int32_t* col, const int32_t* row_of, int64_t nnz, const int64_t* graph_ptr, int64_t G,
+                             int32_t* first_bad, mp_stream_t stream);
+
+/* ------------------------------------------------------------------ *
  * Structural labels and features (graphgym/models/feature_augment.py)  *
  * The engine's CSR, columns ascending inside a row.  Integer results:  *
  * bit-reproducible.  Nothing is allocated, no synchronisation.         *
