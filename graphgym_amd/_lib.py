@@ -72,6 +72,15 @@ PROTOTYPES = {
                                            _p, _p, _p, _p, _sz, _p]),
     "mp_bn_train_bwd_skip_f32": (C.c_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _i32, _p, _p, _p, _p, _i64, _p, _i64, _p,
                                            _p, _p, _sz, _p]),
+    "mp_bn_act_ws_bytes": (C.c_int, [_i64, _i32, _psz]),
+    "mp_bn_train_fwd_act_f32": (C.c_int, [_p, _i64, _i64, _i32, _p, _p, _f32, C.c_int, _f32, _p, _p, _i64, _p, _p, _p, _p,
+                                          _sz, _p]),
+    "mp_bn_train_bwd_act_f32": (C.c_int, [_p, _i64, _p, _i64, _i64, _i32, _p, _p, _p, _p, C.c_int, _f32, _p, _p, _i64, _p,
+                                          _p, _p, _p, _sz, _p]),
+    "mp_bn_train_fwd_skip_act_f32": (C.c_int, [_p, _i64, _p, _i64, _i64, _i32, _i32, C.c_int, _p, _p, _f32, C.c_int, _f32,
+                                               _p, _p, _i64, _p, _p, _p, _p, _sz, _p]),
+    "mp_bn_train_bwd_skip_act_f32": (C.c_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _i32, _i32, C.c_int, _p, _p, _p, _p,
+                                               C.c_int, _f32, _p, _p, _i64, _p, _i64, _p, _p, _p, _p, _sz, _p]),
     "mp_agg_rows_tiles_f32": (C.c_int, [_p, _p, _p, _i64, C.c_int, _p, _i64, _i32, _p, _i64, C.c_float, _p, _i64, _p]),
     "mp_agg_rows_tiles_hot_f32": (C.c_int, [_p, _p, _p, _i64, C.c_int, _p, _i64, _i32, _p, _i64, C.c_float, _p, _i64, _p]),
     "mp_agg_dense_f32": (C.c_int, [_p, _p, _p, _i64, C.c_int, _p, _i64, _i32, _p, _i64, C.c_float, _p, _i64, _i32, _p, C.c_int,

@@ -11,11 +11,15 @@
 //             apply  : read dy (, y), x, write  -> dx = A * g + B * x + C   (per-column constants)
 //   skip block  apply  : read x, skip, write out  -> out = act(skip + BN(x)) or [act(skip) | act(BN(x))]  (gnn.py:49-60)
 //               bwd    : the statistics pass writes g (= d skip), the apply pass reads it: 7 instead of 8 N d
+//   any activation of act.h (the *_act entries): the same passes with act_fwd<ACT> in the apply pass and, backward,
+//             g = dy * act'(z) with z recomputed from x (and skip) — the forward's output is never read; PRELU's slope
+//             gradient is a third sum of the statistics pass, one partial per workgroup
 // Column sums are accumulated per workgroup over a contiguous run of rows (fp32, <= a few thousand terms
 // per lane), written as partial slabs and combined in double precision in slab order: deterministic and
 // accurate at 10^7 rows.
 #include "common.h"
 #include "vecio.h"
+#include "act.h"
 
 namespace mp {
 
@@ -347,6 +351,284 @@ __global__ __launch_bounds__(kBlock) void bn_apply_skip_kernel(const float* __re
   }
 }
 
+// ---- the same passes with any activation of act.h ----------------------------------------------------------------------
+// ACT is a template parameter; `prm` is the kind's host parameter (LRELU's slope, ELU's alpha) and `slope` the device
+// pointer to PRELU's one learnable slope, read here and never on the host.
+template <int ACT>
+__device__ __forceinline__ float act_param(float prm, const float* __restrict__ slope) {
+  if constexpr (ACT == MP_ACT_PRELU) return slope[0];
+  else return prm;
+}
+
+// the sum of one value per thread over the workgroup, in double and in thread order: 16 threads add 16 values each,
+// thread 0 adds the 16 sums and stores
+__device__ __forceinline__ void bn_block_sum(float c, float* __restrict__ dst) {
+  __shared__ float v[kBlock];
+  __shared__ double w[16];
+  v[threadIdx.x] = c;
+  __syncthreads();
+  if (threadIdx.x < 16) {
+    double s = 0.0;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) s += (double)v[threadIdx.x * 16 + q];
+    w[threadIdx.x] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = 0.0;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) s += w[q];
+    *dst = (float)s;
+  }
+}
+
+// forward apply: out = act((x - ctr) * p0 + p1), bn_apply_kernel<W, 0>'s fmaf
+template <int W, int ACT>
+__global__ __launch_bounds__(kBlock) void bn_apply_act_kernel(const float* __restrict__ x, int64_t ldx,
+                                                              const float* __restrict__ p0,
+                                                              const float* __restrict__ p1,
+                                                              const float* __restrict__ ctr, float prm,
+                                                              const float* __restrict__ slope, int64_t N, int32_t d,
+                                                              float* __restrict__ out, int64_t ldo) {
+  const float ap = act_param<ACT>(prm, slope);
+  const int groups = (d + W - 1) / W;
+  const int64_t total = N * groups;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / groups;
+    const int c0 = (int)(i - r * groups) * W;
+    float xv[W], a[W], b[W], o[W], mv[W];
+    load_vec<W>(x + r * ldx + c0, xv);
+    load_vec<W>(p0 + c0, a);
+    load_vec<W>(p1 + c0, b);
+    load_vec<W>(ctr + c0, mv);
+#pragma unroll
+    for (int k = 0; k < W; ++k) o[k] = act_fwd<ACT>(fmaf(xv[k] - mv[k], a[k], b[k]), ap);
+    store_vec<W>(out + r * ldo + c0, o);
+  }
+}
+
+// bn_apply_skip_kernel with act_fwd<ACT> in place of the ReLU
+template <int WS, int WX, bool CONCAT, int ACT>
+__global__ __launch_bounds__(kBlock) void bn_apply_skip_act_kernel(const float* __restrict__ x, int64_t ldx,
+                                                                   const float* __restrict__ skip, int64_t ldskip,
+                                                                   const float* __restrict__ p0,
+                                                                   const float* __restrict__ p1,
+                                                                   const float* __restrict__ ctr, float prm,
+                                                                   const float* __restrict__ slope, int64_t N,
+                                                                   int32_t d, int32_t d_skip, float* __restrict__ out,
+                                                                   int64_t ldo) {
+  const float ap = act_param<ACT>(prm, slope);
+  const int gs = CONCAT ? (d_skip + WS - 1) / WS : 0;
+  const int groups = gs + (d + WX - 1) / WX;
+  const int64_t total = N * groups;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / groups;
+    const int j = (int)(i - r * groups);
+    if (CONCAT && j < gs) {
+      const int c0 = j * WS;
+      float sv[WS];
+      load_vec<WS>(skip + r * ldskip + c0, sv);
+#pragma unroll
+      for (int k = 0; k < WS; ++k) sv[k] = act_fwd<ACT>(sv[k], ap);
+      store_vec<WS>(out + r * ldo + c0, sv);
+    } else {
+      const int c0 = (j - gs) * WX;
+      float xv[WX], a[WX], b[WX], o[WX], mv[WX];
+      load_vec<WX>(x + r * ldx + c0, xv);
+      load_vec<WX>(p0 + c0, a);
+      load_vec<WX>(p1 + c0, b);
+      load_vec<WX>(ctr + c0, mv);
+#pragma unroll
+      for (int k = 0; k < WX; ++k) o[k] = fmaf(xv[k] - mv[k], a[k], b[k]);
+      if (!CONCAT) {
+        float sv[WX];
+        load_vec<WX>(skip + r * ldskip + c0, sv);
+#pragma unroll
+        for (int k = 0; k < WX; ++k) o[k] = sv[k] + o[k];
+      }
+#pragma unroll
+      for (int k = 0; k < WX; ++k) o[k] = act_fwd<ACT>(o[k], ap);
+      store_vec<WX>(out + r * ldo + (CONCAT ? d_skip : 0) + c0, o);
+    }
+  }
+}
+
+// backward statistics: bn_colsum_kernel's MODE 1 / 2 with the pre-activation recomputed from x — z = fmaf(x - mean,
+// float(gamma * invstd), beta), the forward's own expression, plus `skip` when given (the SUM skip block) — and
+// g = dy * act'(z); g goes to gout when given (SUM: d skip).  The two column sums and their partial slabs are
+// bn_colsum_kernel's.  PRELU carries a third sum, dy * min(z, 0) (d out / d slope), over the workgroup's rows AND
+// columns: one value per workgroup in partial3, added in thread order.
+template <int W, int ACT>
+__global__ __launch_bounds__(kBlock) void bn_colsum_act_kernel(const float* __restrict__ x, int64_t ldx,
+                                                               const float* __restrict__ dy, int64_t lddy,
+                                                               const float* __restrict__ skip, int64_t ldskip,
+                                                               const float* __restrict__ mean,
+                                                               const float* __restrict__ gamma,
+                                                               const float* __restrict__ beta,
+                                                               const float* __restrict__ invstd, float prm,
+                                                               const float* __restrict__ slope, int64_t N, int32_t d,
+                                                               int64_t rows_per_block, float* __restrict__ partial,
+                                                               float* __restrict__ partial3,
+                                                               float* __restrict__ gout, int64_t ldg) {
+  __shared__ float red[2][kBlock][W];
+  const float ap = act_param<ACT>(prm, slope);
+  const BnGeom g = bn_geom<W>(d);
+  const int cgi = threadIdx.x % g.cg;
+  const int rli = threadIdx.x / g.cg;
+  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
+  const int64_t r1 = r0 + rows_per_block < N ? r0 + rows_per_block : N;
+  float c3 = 0.f;
+  for (int t = 0; t < g.tiles; ++t) {
+    const int c0 = (t * g.cg + cgi) * W;
+    const bool on = c0 < d;
+    float a[W], b[W], pv[W], sc[W], bt[W];
+#pragma unroll
+    for (int k = 0; k < W; ++k) { a[k] = 0.f; b[k] = 0.f; pv[k] = 0.f; sc[k] = 0.f; bt[k] = 0.f; }
+    if (on) {
+      load_vec<W>(mean + c0, pv);
+#pragma unroll
+      for (int k = 0; k < W; ++k)
+        if (c0 + k < d) {
+          sc[k] = bn_scale(gamma ? gamma[c0 + k] : 1.f, invstd[c0 + k]);
+          bt[k] = beta ? beta[c0 + k] : 0.f;
+        }
+      for (int64_t r = r0 + rli; r < r1; r += g.rl) {
+        float xv[W], gv[W], z[W];
+        load_vec<W>(x + r * ldx + c0, xv);
+        load_vec<W>(dy + r * lddy + c0, gv);
+#pragma unroll
+        for (int k = 0; k < W; ++k) z[k] = fmaf(xv[k] - pv[k], sc[k], bt[k]);
+        if (skip != nullptr) {
+          float sv[W];
+          load_vec<W>(skip + r * ldskip + c0, sv);
+#pragma unroll
+          for (int k = 0; k < W; ++k) z[k] = sv[k] + z[k];
+        }
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+          if (ACT == MP_ACT_PRELU) c3 = fmaf(gv[k], act_dslope(z[k]), c3);
+          gv[k] = act_bwd<ACT>(gv[k], z[k], ap);
+        }
+        if (gout != nullptr) store_vec<W>(gout + r * ldg + c0, gv);
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+          a[k] += gv[k];
+          b[k] = fmaf(gv[k], xv[k] - pv[k], b[k]);
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < W; ++k) { red[0][threadIdx.x][k] = a[k]; red[1][threadIdx.x][k] = b[k]; }
+    __syncthreads();
+    if (rli == 0 && on) {
+#pragma unroll
+      for (int k = 0; k < W; ++k) {
+        float sa = 0.f, sb = 0.f;
+        for (int q = 0; q < g.rl; ++q) { sa += red[0][q * g.cg + cgi][k]; sb += red[1][q * g.cg + cgi][k]; }
+        if (c0 + k < d) {
+          partial[((int64_t)blockIdx.x * 2 + 0) * d + c0 + k] = sa;
+          partial[((int64_t)blockIdx.x * 2 + 1) * d + c0 + k] = sb;
+        }
+      }
+    }
+    __syncthreads();
+  }
+  if (ACT == MP_ACT_PRELU) bn_block_sum(c3, partial3 + blockIdx.x);
+}
+
+// backward apply: dx = A g + B (x - mean) + C with g = dy * act'(z) recomputed as in bn_colsum_act_kernel
+template <int W, int ACT>
+__global__ __launch_bounds__(kBlock) void bn_apply_bwd_act_kernel(const float* __restrict__ x, int64_t ldx,
+                                                                  const float* __restrict__ dy, int64_t lddy,
+                                                                  const float* __restrict__ skip, int64_t ldskip,
+                                                                  const float* __restrict__ A,
+                                                                  const float* __restrict__ B,
+                                                                  const float* __restrict__ Cc,
+                                                                  const float* __restrict__ mean,
+                                                                  const float* __restrict__ fwd_scale,
+                                                                  const float* __restrict__ beta, float prm,
+                                                                  const float* __restrict__ slope, int64_t N,
+                                                                  int32_t d, float* __restrict__ out, int64_t ldo) {
+  const float ap = act_param<ACT>(prm, slope);
+  const int groups = (d + W - 1) / W;
+  const int64_t total = N * groups;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / groups;
+    const int c0 = (int)(i - r * groups) * W;
+    float xv[W], a[W], b[W], cv[W], o[W], mv[W], gv[W], sck[W], btk[W], z[W];
+    load_vec<W>(x + r * ldx + c0, xv);
+    load_vec<W>(dy + r * lddy + c0, gv);
+    load_vec<W>(A + c0, a);
+    load_vec<W>(B + c0, b);
+    load_vec<W>(Cc + c0, cv);
+    load_vec<W>(mean + c0, mv);
+    load_vec<W>(fwd_scale + c0, sck);
+#pragma unroll
+    for (int k = 0; k < W; ++k) btk[k] = 0.f;
+    if (beta != nullptr) load_vec<W>(beta + c0, btk);
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      xv[k] -= mv[k];
+      z[k] = fmaf(xv[k], sck[k], btk[k]);
+    }
+    if (skip != nullptr) {
+      float sv[W];
+      load_vec<W>(skip + r * ldskip + c0, sv);
+#pragma unroll
+      for (int k = 0; k < W; ++k) z[k] = sv[k] + z[k];
+    }
+#pragma unroll
+    for (int k = 0; k < W; ++k) o[k] = fmaf(a[k], act_bwd<ACT>(gv[k], z[k], ap), fmaf(b[k], xv[k], cv[k]));
+    store_vec<W>(out + r * ldo + c0, o);
+  }
+}
+
+// the left slab of the CONCAT skip block's backward: dskip = dy * act'(skip) over [N, ds] (dskip NULL: not asked for),
+// and for PRELU the workgroup's sum of dy * min(skip, 0) in partial3[block].  A workgroup owns bn_colsum's run of rows.
+template <int W, int ACT>
+__global__ __launch_bounds__(kBlock) void bn_act_bwd_left_kernel(const float* __restrict__ dy, int64_t lddy,
+                                                                 const float* __restrict__ skip, int64_t ldskip,
+                                                                 float prm, const float* __restrict__ slope, int64_t N,
+                                                                 int32_t ds, int64_t rows_per_block,
+                                                                 float* __restrict__ dskip, int64_t lddskip,
+                                                                 float* __restrict__ partial3) {
+  const float ap = act_param<ACT>(prm, slope);
+  const int groups = (ds + W - 1) / W;
+  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
+  const int64_t r1 = r0 + rows_per_block < N ? r0 + rows_per_block : N;
+  const int64_t total = r1 > r0 ? (r1 - r0) * groups : 0;
+  float c3 = 0.f;
+  for (int64_t i = threadIdx.x; i < total; i += kBlock) {
+    const int64_t r = r0 + i / groups;
+    const int c0 = (int)(i % groups) * W;
+    float gv[W], sv[W];
+    load_vec<W>(dy + r * lddy + c0, gv);
+    load_vec<W>(skip + r * ldskip + c0, sv);
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      if (ACT == MP_ACT_PRELU) c3 = fmaf(gv[k], act_dslope(sv[k]), c3);
+      gv[k] = act_bwd<ACT>(gv[k], sv[k], ap);
+    }
+    if (dskip != nullptr) store_vec<W>(dskip + r * lddskip + c0, gv);
+  }
+  if (ACT == MP_ACT_PRELU) bn_block_sum(c3, partial3 + blockIdx.x);
+}
+
+// PRELU: the n per-workgroup sums of the statistics pass(es) -> ONE fp32 d slope, in double and in a fixed order
+__global__ __launch_bounds__(kBlock) void bn_dslope_finalize_kernel(const float* __restrict__ partial3, int n,
+                                                                    float* __restrict__ dslope) {
+  __shared__ double v[kBlock];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n; i += kBlock) s += (double)partial3[i];
+  v[threadIdx.x] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+    for (int q = 0; q < kBlock; ++q) t += v[q];
+    dslope[0] = (float)t;
+  }
+}
+
 static int bn_blocks(int64_t N) {
   int64_t b = ceil_div(N, 64);
   if (b < 1) b = 1;
@@ -365,6 +647,17 @@ static void bn_ws_layout(int64_t N, int32_t d, void* base, BnWs* w) {
   for (int i = 0; i < 5; ++i) w->v[i] = (float*)take((size_t)d * 4);
   w->total = off;
 }
+
+// the workspace of the *_act entries: mp_bn_ws_bytes' layout, then PRELU's per-workgroup sums (the BN slab's, then the
+// CONCAT left slab's)
+struct BnActWs { BnWs bn; float* partial3; size_t total; };
+static void bn_act_ws_layout(int64_t N, int32_t d, void* base, BnActWs* w) {
+  bn_ws_layout(N, d, base, &w->bn);
+  w->partial3 = base ? (float*)((char*)base + w->bn.total) : nullptr;
+  w->total = w->bn.total + align_up((size_t)2 * kBnMaxBlocks * 4, 256);
+}
+
+static bool act_known(int act) { return act >= MP_ACT_NONE && act <= MP_ACT_SILU; }
 
 }  // namespace mp
 
@@ -534,6 +827,218 @@ int mp_bn_train_bwd_skip_f32(const float* dy, int64_t lddy, const float* out, in
   // out NULL = no activation: d(skip) is dy itself and nothing is written for it
   return bn_bwd_common(dy, lddy, out, ldo, x, ldx, N, d, gamma, nullptr, 0, mean, invstd, dx, lddx, dgamma, dbeta, ws,
                        ws_bytes, as_stream(stream), out ? dskip : nullptr, out ? lddskip : 0);
+}
+
+// ---- any activation of act.h: MP_ACT_NONE and MP_ACT_RELU go to the entries above where those compute the same ------
+int mp_bn_act_ws_bytes(int64_t N, int32_t d, size_t* bytes_host) {
+  if (!bytes_host || N < 0 || d <= 0) return MP_ERR_INVALID_ARG;
+  BnActWs w;
+  bn_act_ws_layout(N, d, nullptr, &w);
+  *bytes_host = w.total;
+  return MP_OK;
+}
+
+int mp_bn_train_fwd_act_f32(const float* x, int64_t ldx, int64_t N, int32_t d, const float* gamma, const float* beta,
+                            float eps, int act, float act_param, const float* slope, float* y, int64_t ldy,
+                            float* mean, float* invstd, float* var_unbiased, void* ws, size_t ws_bytes,
+                            mp_stream_t stream) {
+  if (!act_known(act) || (act == MP_ACT_PRELU && !slope)) return MP_ERR_INVALID_ARG;
+  if (N <= 0 || d <= 0 || !x || !y || !mean || !invstd || !var_unbiased || ldx < d || ldy < d) return MP_ERR_INVALID_ARG;
+  BnActWs L;
+  bn_act_ws_layout(N, d, ws, &L);
+  if (!ws || ws_bytes < L.total) return MP_ERR_WORKSPACE;
+  if (act == MP_ACT_NONE || act == MP_ACT_RELU)
+    return mp_bn_train_fwd_f32(x, ldx, N, d, gamma, beta, eps, act == MP_ACT_RELU, y, ldy, mean, invstd, var_unbiased,
+                               ws, ws_bytes, stream);
+  hipStream_t st = as_stream(stream);
+  const bool vec = d % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && bn_al(x, 16) && bn_al(y, 16);
+  const int rc = bn_fwd_stats(x, ldx, N, d, gamma, beta, eps, mean, invstd, var_unbiased, L.bn, vec, st);
+  if (rc != MP_OK) return rc;
+  with_act(act, [&](auto a) {
+    constexpr int A = decltype(a)::value;
+    if constexpr (A != MP_ACT_RELU) {      // RELU went to mp_bn_train_fwd_f32 above
+      if (vec)
+        hipLaunchKernelGGL((bn_apply_act_kernel<4, A>), dim3(flat_grid(N * (d / 4))), dim3(kBlock), 0, st, x, ldx,
+                           L.bn.v[0], L.bn.v[1], mean, act_param, slope, N, d, y, ldy);
+      else
+        hipLaunchKernelGGL((bn_apply_act_kernel<1, A>), dim3(flat_grid(N * d)), dim3(kBlock), 0, st, x, ldx, L.bn.v[0],
+                           L.bn.v[1], mean, act_param, slope, N, d, y, ldy);
+    }
+  });
+  MP_LAUNCH_CHECK();
+  return MP_OK;
+}
+
+int mp_bn_train_fwd_skip_act_f32(const float* x, int64_t ldx, const float* skip, int64_t ldskip, int64_t N, int32_t d,
+                                 int32_t d_skip, int mode, const float* gamma, const float* beta, float eps, int act,
+                                 float act_param, const float* slope, float* out, int64_t ldo, float* mean,
+                                 float* invstd, float* var_unbiased, void* ws, size_t ws_bytes, mp_stream_t stream) {
+  if (!act_known(act) || (act == MP_ACT_PRELU && !slope)) return MP_ERR_INVALID_ARG;
+  if (N <= 0 || d <= 0 || d_skip <= 0 || !x || !skip || !out || !mean || !invstd || !var_unbiased || ldx < d ||
+      ldskip < d_skip)
+    return MP_ERR_INVALID_ARG;
+  if (mode != MP_BN_SKIP_SUM && mode != MP_BN_SKIP_CONCAT) return MP_ERR_INVALID_ARG;
+  if (mode == MP_BN_SKIP_SUM && d_skip != d) return MP_ERR_INVALID_ARG;
+  const bool cat = mode == MP_BN_SKIP_CONCAT;
+  if (ldo < (cat ? (int64_t)d_skip + d : (int64_t)d)) return MP_ERR_INVALID_ARG;
+  BnActWs L;
+  bn_act_ws_layout(N, d, ws, &L);
+  if (!ws || ws_bytes < L.total) return MP_ERR_WORKSPACE;
+  if (act == MP_ACT_NONE || act == MP_ACT_RELU)
+    return mp_bn_train_fwd_skip_f32(x, ldx, skip, ldskip, N, d, d_skip, mode, gamma, beta, eps, act == MP_ACT_RELU, out,
+                                    ldo, mean, invstd, var_unbiased, ws, ws_bytes, stream);
+  hipStream_t st = as_stream(stream);
+  // the vector forms of mp_bn_train_fwd_skip_f32
+  const bool vx = d % 4 == 0 && ldx % 4 == 0 && bn_al(x, 16);
+  const bool vo = ldo % 4 == 0 && bn_al(out, 16);
+  const bool vs = d_skip % 4 == 0 && ldskip % 4 == 0 && bn_al(skip, 16) && vo;
+  const int rc = bn_fwd_stats(x, ldx, N, d, gamma, beta, eps, mean, invstd, var_unbiased, L.bn, vx, st);
+  if (rc != MP_OK) return rc;
+#define MP_BN_SKIP_LAUNCH(WS, WX, CAT)                                                                              \
+  hipLaunchKernelGGL((bn_apply_skip_act_kernel<WS, WX, CAT, A>),                                                    \
+                     dim3(flat_grid(N * ((CAT ? (int64_t)d_skip / WS : 0) + (int64_t)d / WX))), dim3(kBlock), 0, st, \
+                     x, ldx, skip, ldskip, L.bn.v[0], L.bn.v[1], mean, act_param, slope, N, d, d_skip, out, ldo)
+  with_act(act, [&](auto a) {
+    constexpr int A = decltype(a)::value;
+    if constexpr (A != MP_ACT_RELU) {      // RELU went to mp_bn_train_fwd_skip_f32 above
+      if (!cat) {
+        if (vx && vs) MP_BN_SKIP_LAUNCH(4, 4, false);
+        else MP_BN_SKIP_LAUNCH(1, 1, false);
+      } else {
+        const bool vr = vx && vo && d_skip % 4 == 0;      // the right slab starts at out + d_skip
+        if (vs && vr) MP_BN_SKIP_LAUNCH(4, 4, true);
+        else if (vs) MP_BN_SKIP_LAUNCH(4, 1, true);
+        else if (vr) MP_BN_SKIP_LAUNCH(1, 4, true);
+        else MP_BN_SKIP_LAUNCH(1, 1, true);
+      }
+    }
+  });
+#undef MP_BN_SKIP_LAUNCH
+  MP_LAUNCH_CHECK();
+  return MP_OK;
+}
+
+}  // extern "C"
+
+// statistics, finalize and apply of a backward whose g = dy * act'(z) is recomputed from x (and skip: SUM).  gout != NULL:
+// the statistics pass writes g there and the apply pass reads it in place of dy, x's affine and skip (the 7 N d scheme
+// of mp_bn_train_bwd_skip_f32).  PRELU leaves its per-workgroup sums in L.partial3[0 .. bn_blocks(N)).
+template <int ACT>
+static int bn_bwd_act_launch(const float* dy, int64_t lddy, const float* x, int64_t ldx, const float* skip,
+                             int64_t ldskip, int64_t N, int32_t d, const float* gamma, const float* beta,
+                             const float* mean, const float* invstd, float prm, const float* slope, float* dx,
+                             int64_t lddx, float* gout, int64_t ldg, float* dgamma, float* dbeta, const BnActWs& L,
+                             hipStream_t st) {
+  const int nblk = bn_blocks(N);
+  const int64_t rpb = ceil_div(N, nblk);
+  const bool vec = d % 4 == 0 && ldx % 4 == 0 && lddy % 4 == 0 && lddx % 4 == 0 && bn_al(x, 16) && bn_al(dy, 16) &&
+                   bn_al(dx, 16) && bn_al(beta, 16) && ldskip % 4 == 0 && bn_al(skip, 16) && ldg % 4 == 0 &&
+                   bn_al(gout, 16);
+  const BnWs& B = L.bn;
+  if (vec)
+    hipLaunchKernelGGL((bn_colsum_act_kernel<4, ACT>), dim3(nblk), dim3(kBlock), 0, st, x, ldx, dy, lddy, skip, ldskip,
+                       mean, gamma, beta, invstd, prm, slope, N, d, rpb, B.partial, L.partial3, gout, ldg);
+  else
+    hipLaunchKernelGGL((bn_colsum_act_kernel<1, ACT>), dim3(nblk), dim3(kBlock), 0, st, x, ldx, dy, lddy, skip, ldskip,
+                       mean, gamma, beta, invstd, prm, slope, N, d, rpb, B.partial, L.partial3, gout, ldg);
+  MP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)ceil_div(d, 16)), dim3(kBlock), 0, st, B.partial, nblk, N,
+                     d, gamma, mean, invstd, dgamma, dbeta, B.v[0], B.v[1], B.v[2], B.v[3]);
+  MP_LAUNCH_CHECK();
+  if (gout != nullptr) {      // g is on hand
+    if (vec)
+      hipLaunchKernelGGL((bn_apply_kernel<4, 1>), dim3(flat_grid(N * (d / 4))), dim3(kBlock), 0, st, x, ldx, gout, ldg,
+                         nullptr, 0, B.v[0], B.v[1], B.v[2], mean, 0, N, d, dx, lddx, nullptr, nullptr);
+    else
+      hipLaunchKernelGGL((bn_apply_kernel<1, 1>), dim3(flat_grid(N * d)), dim3(kBlock), 0, st, x, ldx, gout, ldg,
+                         nullptr, 0, B.v[0], B.v[1], B.v[2], mean, 0, N, d, dx, lddx, nullptr, nullptr);
+  } else if (vec) {
+    hipLaunchKernelGGL((bn_apply_bwd_act_kernel<4, ACT>), dim3(flat_grid(N * (d / 4))), dim3(kBlock), 0, st, x, ldx, dy,
+                       lddy, skip, ldskip, B.v[0], B.v[1], B.v[2], mean, B.v[3], beta, prm, slope, N, d, dx, lddx);
+  } else {
+    hipLaunchKernelGGL((bn_apply_bwd_act_kernel<1, ACT>), dim3(flat_grid(N * d)), dim3(kBlock), 0, st, x, ldx, dy, lddy,
+                       skip, ldskip, B.v[0], B.v[1], B.v[2], mean, B.v[3], beta, prm, slope, N, d, dx, lddx);
+  }
+  MP_LAUNCH_CHECK();
+  return MP_OK;
+}
+
+static int bn_dslope_finalize(const BnActWs& L, int n, float* dslope, hipStream_t st) {
+  hipLaunchKernelGGL(bn_dslope_finalize_kernel, dim3(1), dim3(kBlock), 0, st, L.partial3, n, dslope);
+  MP_LAUNCH_CHECK();
+  return MP_OK;
+}
+
+extern "C" {
+
+int mp_bn_train_bwd_act_f32(const float* dy, int64_t lddy, const float* x, int64_t ldx, int64_t N, int32_t d,
+                            const float* gamma, const float* beta, const float* mean, const float* invstd, int act,
+                            float act_param, const float* slope, float* dx, int64_t lddx, float* dgamma, float* dbeta,
+                            float* dslope, void* ws, size_t ws_bytes, mp_stream_t stream) {
+  if (!act_known(act) || (act == MP_ACT_PRELU && !slope)) return MP_ERR_INVALID_ARG;
+  if (N <= 0 || d <= 0 || !dy || !x || !mean || !invstd || !dx || lddy < d || ldx < d || lddx < d)
+    return MP_ERR_INVALID_ARG;
+  BnActWs L;
+  bn_act_ws_layout(N, d, ws, &L);
+  if (!ws || ws_bytes < L.total) return MP_ERR_WORKSPACE;
+  hipStream_t st = as_stream(stream);
+  if (act == MP_ACT_NONE || act == MP_ACT_RELU)
+    return bn_bwd_common(dy, lddy, nullptr, 0, x, ldx, N, d, gamma, beta, act == MP_ACT_RELU, mean, invstd, dx, lddx,
+                         dgamma, dbeta, ws, ws_bytes, st);
+  int rc = MP_OK;
+  with_act(act, [&](auto a) {
+    rc = bn_bwd_act_launch<decltype(a)::value>(dy, lddy, x, ldx, nullptr, 0, N, d, gamma, beta, mean, invstd, act_param,
+                                               slope, dx, lddx, nullptr, 0, dgamma, dbeta, L, st);
+  });
+  if (rc != MP_OK) return rc;
+  if (act == MP_ACT_PRELU && dslope) return bn_dslope_finalize(L, bn_blocks(N), dslope, st);
+  return MP_OK;
+}
+
+int mp_bn_train_bwd_skip_act_f32(const float* dy, int64_t lddy, const float* x, int64_t ldx, const float* skip,
+                                 int64_t ldskip, int64_t N, int32_t d, int32_t d_skip, int mode, const float* gamma,
+                                 const float* beta, const float* mean, const float* invstd, int act, float act_param,
+                                 const float* slope, float* dx, int64_t lddx, float* dskip, int64_t lddskip,
+                                 float* dgamma, float* dbeta, float* dslope, void* ws, size_t ws_bytes,
+                                 mp_stream_t stream) {
+  if (!act_known(act) || (act == MP_ACT_PRELU && !slope)) return MP_ERR_INVALID_ARG;
+  if (mode != MP_BN_SKIP_SUM && mode != MP_BN_SKIP_CONCAT) return MP_ERR_INVALID_ARG;
+  const bool cat = mode == MP_BN_SKIP_CONCAT;
+  if (N <= 0 || d <= 0 || d_skip <= 0 || (!cat && d_skip != d) || !dy || !x || !skip || !mean || !invstd || !dx ||
+      lddy < (cat ? (int64_t)d_skip + d : (int64_t)d) || ldx < d || ldskip < d_skip || lddx < d ||
+      (dskip && lddskip < d_skip))
+    return MP_ERR_INVALID_ARG;
+  BnActWs L;
+  bn_act_ws_layout(N, d, ws, &L);
+  if (!ws || ws_bytes < L.total) return MP_ERR_WORKSPACE;
+  hipStream_t st = as_stream(stream);
+  const float* dyr = cat ? dy + d_skip : dy;      // the BN slab of dy
+  if (act == MP_ACT_NONE)      // d(skip) is dy (its left slab) itself: dskip is not written
+    return bn_bwd_common(dyr, lddy, nullptr, 0, x, ldx, N, d, gamma, nullptr, 0, mean, invstd, dx, lddx, dgamma, dbeta,
+                         ws, ws_bytes, st);
+  const int nblk = bn_blocks(N);
+  const bool left = cat && (dskip || (act == MP_ACT_PRELU && dslope));
+  const bool vl = d_skip % 4 == 0 && lddy % 4 == 0 && ldskip % 4 == 0 && bn_al(dy, 16) && bn_al(skip, 16) &&
+                  (!dskip || (lddskip % 4 == 0 && bn_al(dskip, 16)));
+  int rc = MP_OK;
+  with_act(act, [&](auto a) {
+    constexpr int A = decltype(a)::value;
+    rc = bn_bwd_act_launch<A>(dyr, lddy, x, ldx, cat ? nullptr : skip, cat ? 0 : ldskip, N, d, gamma, beta, mean, invstd,
+                              act_param, slope, dx, lddx, cat ? nullptr : dskip, cat ? 0 : lddskip, dgamma, dbeta, L,
+                              st);
+    if (rc != MP_OK || !left) return;
+    const int64_t rpb = ceil_div(N, nblk);
+    if (vl)
+      hipLaunchKernelGGL((bn_act_bwd_left_kernel<4, A>), dim3(nblk), dim3(kBlock), 0, st, dy, lddy, skip, ldskip,
+                         act_param, slope, N, d_skip, rpb, dskip, lddskip, L.partial3 + nblk);
+    else
+      hipLaunchKernelGGL((bn_act_bwd_left_kernel<1, A>), dim3(nblk), dim3(kBlock), 0, st, dy, lddy, skip, ldskip,
+                         act_param, slope, N, d_skip, rpb, dskip, lddskip, L.partial3 + nblk);
+  });
+  if (rc != MP_OK) return rc;
+  MP_LAUNCH_CHECK();
+  if (act == MP_ACT_PRELU && dslope) return bn_dslope_finalize(L, cat ? 2 * nblk : nblk, dslope, st);
+  return MP_OK;
 }
 
 }  // extern "C"

@@ -142,12 +142,22 @@ class GeneralLayer(nn.Module):
             post.append(_act_module())
         self.post_layer = nn.Sequential(*post)
 
+    def _post(self, x):
+        """post_layer; [BatchNorm1d, an activation graphgym_amd.nn.act_spec knows] in training mode on a device fp32
+        tensor is ONE engine op (nn.bn_act_module).  The modules stay where they are: a PReLU's slope is
+        post_layer.1.weight in the state dict either way."""
+        post = self.post_layer
+        if (len(post) == 2 and type(post[0]) is mpnn.BatchNorm1d and not post[0].relu and post[0].training
+                and mpnn.act_spec(post[1]) is not None and x.dim() == 2 and x.is_cuda and x.dtype == torch.float32):
+            return mpnn.bn_act_module(post[0], x, post[1])
+        return post(x)
+
     def forward(self, batch):
         batch = self.layer(batch)
         if isinstance(batch, torch.Tensor):                      # layer.py:39-42 (the head's MLP passes tensors)
-            batch = self.post_layer(batch)
+            batch = self._post(batch)
             return F.normalize(batch, p=2, dim=1) if self.has_l2norm else batch
-        batch.node_feature = self.post_layer(batch.node_feature)
+        batch.node_feature = self._post(batch.node_feature)
         if self.has_l2norm:
             batch.node_feature = F.normalize(batch.node_feature, p=2, dim=1)
         return batch
@@ -257,15 +267,20 @@ def _act_module():
 def skip_block_forward(block, batch, stage_type, orig=None):
     """GNNSkipBlock.forward (gnn.py:49-60) for a block `f` of layer wrappers (`.layer`, `.post_layer`, `.has_l2norm`) and
     an activation `act`.  When the last layer's post-ops are exactly one BatchNorm1d in training mode (no dropout, no
-    fused ReLU of its own) and the block's activation is ReLU, the BatchNorm, the skip add / concatenation and the
-    activation are ONE graphgym_amd.nn.bn_skip_act call behind the last conv; anything else is the reference's
-    composition (`orig(batch)` when given: the forward graphgym_plugin.accelerate() replaced)."""
+    fused ReLU of its own) and the block's activation is ReLU — or, for the harness's own block (`orig` None), any
+    activation graphgym_amd.nn.act_spec knows — the BatchNorm, the skip add / concatenation and the activation are ONE
+    graphgym_amd.nn.bn_skip_act call behind the last conv; anything else is the reference's composition
+    (`orig(batch)` when given: the forward graphgym_plugin.accelerate() replaced)."""
     if stage_type not in ("skipsum", "skipconcat"):
         raise ValueError("cfg.gnn.stage_type must in [skipsum, skipconcat]")
     last = block.f[-1]
     post = list(last.post_layer)
+    # the harness's own block (orig None) takes any activation graphgym_amd.nn.act_spec knows; a block accelerate()
+    # rewired keeps its original forward unless its activation is ReLU
+    relu = type(block.act) is nn.ReLU
+    act_ok = relu or (orig is None and mpnn.act_spec(block.act) is not None)
     fused = (len(post) == 1 and isinstance(post[0], nn.BatchNorm1d) and not getattr(post[0], "relu", False)
-             and (post[0].training or not post[0].track_running_stats) and type(block.act) is nn.ReLU and not last.has_l2norm
+             and (post[0].training or not post[0].track_running_stats) and act_ok and not last.has_l2norm
              and isinstance(batch.node_feature, torch.Tensor) and batch.node_feature.is_cuda)
     if not fused and orig is not None:
         return orig(batch)
@@ -277,7 +292,8 @@ def skip_block_forward(block, batch, stage_type, orig=None):
     for layer in list(block.f)[:-1]:
         batch = layer(batch)
     batch = last.layer(batch)
-    batch.node_feature = mpnn.bn_skip_act(post[0], batch.node_feature, x, stage_type, relu=True)
+    batch.node_feature = mpnn.bn_skip_act(post[0], batch.node_feature, x, stage_type, relu=True,
+                                          act=None if relu else block.act)
     return batch
 
 

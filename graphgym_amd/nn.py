@@ -4,7 +4,8 @@ Drop-in for ``torch.nn.BatchNorm1d`` as GraphGym uses it after every conv (graph
 and as the keras BatchNormalization in the TF path's GIN MLPs (main_zd.py:181-186): same parameter and buffer
 names (weight, bias, running_mean, running_var, num_batches_tracked), same momentum / eps semantics.  In
 training mode the statistics, the normalisation, the optional ReLU and the whole backward run as four
-HBM-bound passes; torch's own kernel needs 0.5 s per backward call on a [10^7, 256] activation.
+HBM-bound passes; torch's own kernel needs 0.5 s per backward call on a [10^7, 256] activation.  Any other activation
+of GraphGym's act_dict (and SiLU) rides the same passes through bn_act_module / bn_skip_act(act=...): act_spec says which.
 """
 import ctypes as C
 from typing import Optional, Tuple
@@ -279,6 +280,283 @@ def _bn_skip_backward(ctx, dy, _dmean, _dinvstd, _dvar):
 register_autograd("mp::bn_skip_act", _bn_skip_backward, setup_context=_bn_skip_setup)
 
 
+# ---- the same passes with any activation of cfg.gnn.act (graphgym/models/act.py:6-14) --------------------------------
+# The unfused composition moves 5 N d elements forward (statistics, BN apply, activation) and 8 N d backward, and keeps
+# x AND the BatchNorm's output for the backward; with the activation in the apply pass it is 3 N d and 5 N d, and x
+# alone is kept: the backward recomputes the pre-activation from x (csrc/bn.hip, csrc/act.h).
+# MP_ACT_* of include/mp_engine.h
+ACT_NONE, ACT_RELU, ACT_LRELU, ACT_PRELU, ACT_ELU, ACT_SELU, ACT_SILU = range(7)
+
+
+def act_spec(module):
+    """(kind, parameter) of an activation module the engine's BatchNorm passes can take along, None for any other:
+    nn.ReLU, nn.SELU, nn.SiLU -> (kind, None); nn.LeakyReLU -> (ACT_LRELU, negative_slope); nn.ELU -> (ACT_ELU, alpha);
+    nn.PReLU() with ONE slope -> (ACT_PRELU, its weight).  Exact types only: a subclass may compute anything."""
+    t = type(module)
+    if t is nn.ReLU:
+        return ACT_RELU, None
+    if t is nn.LeakyReLU:
+        return ACT_LRELU, float(module.negative_slope)
+    if t is nn.PReLU:
+        return (ACT_PRELU, module.weight) if module.num_parameters == 1 else None
+    if t is nn.ELU:
+        return ACT_ELU, float(module.alpha)
+    if t is nn.SELU:
+        return ACT_SELU, None
+    if t is nn.SiLU:
+        return ACT_SILU, None
+    return None
+
+
+def _spec_args(spec):
+    """(slope tensor or None, host parameter) of an act_spec result, as the ops take them"""
+    kind, p = spec
+    return (p if kind == ACT_PRELU else None), (float(p) if kind in (ACT_LRELU, ACT_ELU) else 0.0)
+
+
+def _check_kind(kind, slope):
+    if not ACT_NONE <= kind <= ACT_SILU:
+        raise ValueError(f"unknown activation kind {kind}")
+    if kind == ACT_PRELU and (slope is None or slope.numel() != 1):
+        raise ValueError("ACT_PRELU takes a slope tensor of ONE element (nn.PReLU())")
+
+
+def _slope32(slope, kind):
+    """PRELU's slope as one fp32 element on the device (it is read there, never on the host); None for other kinds"""
+    return slope.detach().reshape(1).float().contiguous() if kind == ACT_PRELU else None
+
+
+def _bn_act_ws(N, d, device):
+    nb = C.c_size_t(0)
+    check(lib().mp_bn_act_ws_bytes(N, d, C.byref(nb)))
+    return torch.empty(nb.value, dtype=torch.uint8, device=device), nb.value
+
+
+def _stats_fake(x):
+    d = x.size(1)
+    return tuple(x.new_empty((d,), dtype=torch.float32) for _ in range(3))
+
+
+@custom_op("mp::bn_actx_fwd_raw", mutates_args=(), device_types="cuda")
+def _op_bn_actx_fwd_raw(x: Tensor, weight: Optional[Tensor], bias: Optional[Tensor], slope: Optional[Tensor],
+                        eps: float, kind: int, param: float) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(y, mean, invstd, unbiased var): y = act(BatchNorm1d(x)) with batch statistics, act = the ACT_* kind"""
+    _require_hip(x, "x")
+    _check_kind(kind, slope)
+    x = _rows32(x)
+    N, d = x.shape
+    y = placement.empty_or_torch((N, d), x.device, reads=(x,), streaming=True)
+    mean = torch.empty(d, dtype=torch.float32, device=x.device)
+    invstd = torch.empty_like(mean)
+    var_u = torch.empty_like(mean)
+    w = None if weight is None else weight.detach().contiguous()
+    b = None if bias is None else bias.detach().contiguous()
+    s = _slope32(slope, kind)
+    with torch.cuda.device(x.device):
+        ws, nb = _bn_act_ws(N, d, x.device)
+        check(lib().mp_bn_train_fwd_act_f32(ptr(x), x.stride(0), N, d, ptr(w), ptr(b), float(eps), kind, float(param),
+                                            ptr(s), ptr(y), y.stride(0), ptr(mean), ptr(invstd), ptr(var_u), ptr(ws),
+                                            nb, _stream()), "mp_bn_train_fwd_act_f32")
+    return y, mean, invstd, var_u
+
+
+@_op_bn_actx_fwd_raw.register_fake
+def _(x, weight, bias, slope, eps, kind, param):
+    return (x.new_empty(x.shape, dtype=torch.float32),) + _stats_fake(x)
+
+
+@custom_op("mp::bn_actx_bwd_raw", mutates_args=(), device_types="cuda")
+def _op_bn_actx_bwd_raw(dy: Tensor, x: Tensor, weight: Optional[Tensor], bias: Optional[Tensor],
+                        slope: Optional[Tensor], mean: Tensor, invstd: Tensor, kind: int, param: float,
+                        want_dslope: bool = True) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(dx, dgamma, dbeta, dslope) of bn_actx_fwd_raw.  The forward's output is not an operand: the pre-activation is
+    recomputed from x, weight, bias, mean, invstd.  dslope: [1] for ACT_PRELU with want_dslope, EMPTY otherwise."""
+    _check_kind(kind, slope)
+    x, dy = _rows32(x), _rows32(dy)
+    N, d = x.shape
+    dx = placement.empty_or_torch((N, d), x.device, reads=(dy, x), streaming=True)
+    dgamma = torch.empty(d, dtype=torch.float32, device=x.device)
+    dbeta = torch.empty_like(dgamma)
+    dslope = torch.empty(1 if (kind == ACT_PRELU and want_dslope) else 0, dtype=torch.float32, device=x.device)
+    w = None if weight is None else weight.detach().contiguous()
+    b = None if bias is None else bias.detach().contiguous()
+    s = _slope32(slope, kind)
+    with torch.cuda.device(x.device):
+        ws, nb = _bn_act_ws(N, d, x.device)
+        check(lib().mp_bn_train_bwd_act_f32(ptr(dy), dy.stride(0), ptr(x), x.stride(0), N, d, ptr(w), ptr(b), ptr(mean),
+                                            ptr(invstd), kind, float(param), ptr(s), ptr(dx), dx.stride(0),
+                                            ptr(dgamma), ptr(dbeta), ptr(dslope) if dslope.numel() else None, ptr(ws),
+                                            nb, _stream()), "mp_bn_train_bwd_act_f32")
+    return dx, dgamma, dbeta, dslope
+
+
+@_op_bn_actx_bwd_raw.register_fake
+def _(dy, x, weight, bias, slope, mean, invstd, kind, param, want_dslope=True):
+    return (x.new_empty(x.shape, dtype=torch.float32),) + _stats_fake(x)[:2] + (
+        x.new_empty((1 if (kind == ACT_PRELU and want_dslope) else 0,), dtype=torch.float32),)
+
+
+@custom_op("mp::bn_actx", mutates_args=(), device_types="cuda")
+def _op_bn_actx(x: Tensor, weight: Optional[Tensor], bias: Optional[Tensor], slope: Optional[Tensor], eps: float,
+                kind: int, param: float) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """graphgym/models/layer.py:26-35 (BatchNorm1d, then cfg.gnn.act) in training mode: (y, mean, invstd, var)"""
+    return torch.ops.mp.bn_actx_fwd_raw(x, weight, bias, slope, eps, kind, param)
+
+
+@_op_bn_actx.register_fake
+def _(x, weight, bias, slope, eps, kind, param):
+    return (x.new_empty(x.shape, dtype=torch.float32),) + _stats_fake(x)
+
+
+def _bn_actx_setup(ctx, inputs, output):
+    x, weight, bias, slope, eps, kind, param = inputs
+    _, mean, invstd, _ = output
+    ctx.kind, ctx.param = kind, param
+    ctx.has = (weight is not None, bias is not None, slope is not None)
+    ctx.slope_shape = None if slope is None else slope.shape
+    ctx.save_for_backward(x, weight, bias, slope, mean, invstd)      # not y: the backward recomputes it from x
+
+
+def _bn_actx_backward(ctx, dy, _dmean, _dinvstd, _dvar):
+    x, w, b, s, mean, invstd = ctx.saved_tensors
+    need_x, need_w, need_b, need_s = ctx.needs_input_grad[:4]
+    need_s = need_s and ctx.kind == ACT_PRELU
+    if not (need_x or need_w or need_b or need_s):
+        return (None,) * 7
+    dx, dgamma, dbeta, dslope = torch.ops.mp.bn_actx_bwd_raw(dy, x, w, b, s, mean, invstd, ctx.kind, ctx.param, need_s)
+    return (dx if need_x else None, dgamma if (need_w and ctx.has[0]) else None,
+            dbeta if (need_b and ctx.has[1]) else None, dslope.reshape(ctx.slope_shape) if need_s else None,
+            None, None, None)
+
+
+register_autograd("mp::bn_actx", _bn_actx_backward, setup_context=_bn_actx_setup)
+
+
+@custom_op("mp::bn_skip_actx_fwd_raw", mutates_args=(), device_types="cuda")
+def _op_bn_skip_actx_fwd_raw(x: Tensor, skip: Tensor, weight: Optional[Tensor], bias: Optional[Tensor],
+                             slope: Optional[Tensor], eps: float, kind: int, param: float,
+                             mode: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """bn_skip_fwd_raw with the ACT_* kind in place of the ReLU switch"""
+    _require_hip(x, "x")
+    _require_hip(skip, "skip")
+    _check_skip_shapes(x, skip, mode)
+    _check_kind(kind, slope)
+    x, skip = _rows32(x), _rows32(skip)
+    N, d = x.shape
+    d_skip = skip.size(1)
+    out = placement.empty_or_torch((N, d if mode == SKIP_SUM else d_skip + d), x.device, reads=(x, skip),
+                                   streaming=True)
+    mean = torch.empty(d, dtype=torch.float32, device=x.device)
+    invstd = torch.empty_like(mean)
+    var_u = torch.empty_like(mean)
+    w = None if weight is None else weight.detach().contiguous()
+    b = None if bias is None else bias.detach().contiguous()
+    s = _slope32(slope, kind)
+    with torch.cuda.device(x.device):
+        ws, nb = _bn_act_ws(N, d, x.device)
+        check(lib().mp_bn_train_fwd_skip_act_f32(ptr(x), x.stride(0), ptr(skip), skip.stride(0), N, d, d_skip, mode,
+                                                 ptr(w), ptr(b), float(eps), kind, float(param), ptr(s), ptr(out),
+                                                 out.stride(0), ptr(mean), ptr(invstd), ptr(var_u), ptr(ws), nb,
+                                                 _stream()), "mp_bn_train_fwd_skip_act_f32")
+    return out, mean, invstd, var_u
+
+
+@_op_bn_skip_actx_fwd_raw.register_fake
+def _(x, skip, weight, bias, slope, eps, kind, param, mode):
+    return _skip_fake(x, skip, mode)
+
+
+@custom_op("mp::bn_skip_actx_bwd_raw", mutates_args=(), device_types="cuda")
+def _op_bn_skip_actx_bwd_raw(dy: Tensor, x: Tensor, skip: Tensor, weight: Optional[Tensor], bias: Optional[Tensor],
+                             slope: Optional[Tensor], mean: Tensor, invstd: Tensor, mode: int, kind: int, param: float,
+                             want_dskip: bool = True,
+                             want_dslope: bool = True) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """(dx, dgamma, dbeta, dskip, dslope) of bn_skip_actx_fwd_raw from x and skip, without the forward's output.
+    SKIP_SUM: the statistics pass writes dskip = dy * act'(skip + BN(x)) and the apply pass reads it back; without
+    want_dskip the apply pass recomputes it.  SKIP_CONCAT: dskip = dy[:, :d_skip] * act'(skip).  dskip comes back EMPTY
+    without want_dskip and for ACT_NONE (d(skip) is dy itself: the caller takes it); dslope as in bn_actx_bwd_raw."""
+    _check_skip_shapes(x, skip, mode)
+    _check_kind(kind, slope)
+    x, skip, dy = _rows32(x), _rows32(skip), _rows32(dy)
+    N, d = x.shape
+    d_skip = skip.size(1)
+    if dy.shape != (N, d if mode == SKIP_SUM else d_skip + d):
+        raise ValueError(f"bn_skip_actx_bwd_raw: dy {tuple(dy.shape)}, x {tuple(x.shape)}, skip {tuple(skip.shape)}, "
+                         f"mode {mode} do not fit")
+    dx = placement.empty_or_torch((N, d), x.device, reads=(dy, x), streaming=True)
+    dgamma = torch.empty(d, dtype=torch.float32, device=x.device)
+    dbeta = torch.empty_like(dgamma)
+    dslope = torch.empty(1 if (kind == ACT_PRELU and want_dslope) else 0, dtype=torch.float32, device=x.device)
+    if want_dskip and kind != ACT_NONE:
+        dskip = placement.empty_or_torch((N, d_skip), x.device, reads=(dy, skip), streaming=True)
+    else:
+        dskip = torch.empty(0, dtype=torch.float32, device=x.device)
+    w = None if weight is None else weight.detach().contiguous()
+    b = None if bias is None else bias.detach().contiguous()
+    s = _slope32(slope, kind)
+    with torch.cuda.device(x.device):
+        ws, nb = _bn_act_ws(N, d, x.device)
+        check(lib().mp_bn_train_bwd_skip_act_f32(ptr(dy), dy.stride(0), ptr(x), x.stride(0), ptr(skip), skip.stride(0),
+                                                 N, d, d_skip, mode, ptr(w), ptr(b), ptr(mean), ptr(invstd), kind,
+                                                 float(param), ptr(s), ptr(dx), dx.stride(0),
+                                                 ptr(dskip) if dskip.numel() else None,
+                                                 dskip.stride(0) if dskip.numel() else 0, ptr(dgamma), ptr(dbeta),
+                                                 ptr(dslope) if dslope.numel() else None, ptr(ws), nb, _stream()),
+              "mp_bn_train_bwd_skip_act_f32")
+    return dx, dgamma, dbeta, dskip, dslope
+
+
+@_op_bn_skip_actx_bwd_raw.register_fake
+def _(dy, x, skip, weight, bias, slope, mean, invstd, mode, kind, param, want_dskip=True, want_dslope=True):
+    dskip = (x.new_empty(skip.shape, dtype=torch.float32) if (want_dskip and kind != ACT_NONE)
+             else x.new_empty((0,), dtype=torch.float32))
+    return (x.new_empty(x.shape, dtype=torch.float32),) + _stats_fake(x)[:2] + (
+        dskip, x.new_empty((1 if (kind == ACT_PRELU and want_dslope) else 0,), dtype=torch.float32))
+
+
+@custom_op("mp::bn_skip_actx", mutates_args=(), device_types="cuda")
+def _op_bn_skip_actx(x: Tensor, skip: Tensor, weight: Optional[Tensor], bias: Optional[Tensor],
+                     slope: Optional[Tensor], eps: float, kind: int, param: float,
+                     mode: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """graphgym/models/gnn.py:49-60 behind a last layer without activation, in training mode, with any cfg.gnn.act:
+    act(skip + BN(x)) or act(cat(skip, BN(x))): (out, mean, invstd, var)"""
+    return torch.ops.mp.bn_skip_actx_fwd_raw(x, skip, weight, bias, slope, eps, kind, param, mode)
+
+
+@_op_bn_skip_actx.register_fake
+def _(x, skip, weight, bias, slope, eps, kind, param, mode):
+    return _skip_fake(x, skip, mode)
+
+
+def _bn_skip_actx_setup(ctx, inputs, output):
+    x, skip, weight, bias, slope, eps, kind, param, mode = inputs
+    _, mean, invstd, _ = output
+    ctx.kind, ctx.param, ctx.mode, ctx.d_skip = kind, param, mode, skip.size(1)
+    ctx.has = (weight is not None, bias is not None, slope is not None)
+    ctx.slope_shape = None if slope is None else slope.shape
+    # skip is kept where out was: the pre-activation is recomputed from x and skip
+    ctx.save_for_backward(x, skip, weight, bias, slope, mean, invstd)
+
+
+def _bn_skip_actx_backward(ctx, dy, _dmean, _dinvstd, _dvar):
+    x, skip, w, b, s, mean, invstd = ctx.saved_tensors
+    need_x, need_skip, need_w, need_b, need_s = ctx.needs_input_grad[:5]
+    need_s = need_s and ctx.kind == ACT_PRELU
+    dx = dgamma = dbeta = dskip = dslope = None
+    none = ctx.kind == ACT_NONE
+    if need_x or need_w or need_b or need_s or (need_skip and not none):
+        dx, dgamma, dbeta, dskip, dslope = torch.ops.mp.bn_skip_actx_bwd_raw(
+            dy, x, skip, w, b, s, mean, invstd, ctx.mode, ctx.kind, ctx.param, need_skip, need_s)
+    if need_skip and none:
+        dskip = dy if ctx.mode == SKIP_SUM else dy[:, :ctx.d_skip]
+    return (dx if need_x else None, dskip if need_skip else None, dgamma if (need_w and ctx.has[0]) else None,
+            dbeta if (need_b and ctx.has[1]) else None, dslope.reshape(ctx.slope_shape) if need_s else None,
+            None, None, None, None)
+
+
+register_autograd("mp::bn_skip_actx", _bn_skip_actx_backward, setup_context=_bn_skip_actx_setup)
+
+
 # ---- softmax cross-entropy over the labelled rows (graphgym/loss.py:53-68, 20-37) -------------------------------
 def _check_ce_shapes(z, y, idx):
     """host-side shape contract (no device read): one label per selected row.  Label VALUES are checked on the device:
@@ -401,26 +679,54 @@ class BatchNorm1d(nn.BatchNorm1d):
         return super().extra_repr() + f", relu={self.relu}"
 
 
+def _bn_on_engine(bn, x):
+    """BatchNorm1d.forward's rule for the fused passes: batch statistics, a device tensor of more than one row, not bf16,
+    and a BatchNorm that carries no fused ReLU of its own"""
+    return (isinstance(bn, nn.BatchNorm1d) and not getattr(bn, "relu", False)
+            and (bn.training or not bn.track_running_stats) and x.dim() == 2 and x.is_cuda and x.size(0) > 1
+            and x.dtype != torch.bfloat16)
+
+
+def bn_act_module(bn, x, act):
+    """``act(bn(x))`` — GraphGym's post-layer (graphgym/models/layer.py:26-35) — for an activation MODULE `act`.  When
+    act_spec knows it and BatchNorm1d.forward's rule holds, this is one engine op (mp::bn_actx): the activation rides the
+    BatchNorm's apply pass, the backward recomputes it from x, and a PReLU slope receives its gradient from the same
+    passes.  Everything else — eval mode, CPU tensors, bf16, a single row, a subclass, per-channel PReLU, a user
+    module — is the torch composition.  `bn`'s running statistics are updated as its own forward would."""
+    spec = act_spec(act)
+    if spec is None or not _bn_on_engine(bn, x):
+        return act(bn(x))
+    slope, param = _spec_args(spec)
+    y, mean, _, var_u = torch.ops.mp.bn_actx(x, bn.weight, bn.bias, slope, float(bn.eps), spec[0], param)
+    _update_running_stats(bn, mean, var_u)
+    return y
+
+
 def bn_skip_act(bn, x, skip, mode, relu=True, act=None):
     """The tail of GraphGym's skip block (graphgym/models/gnn.py:49-60) around its last layer's BatchNorm:
     ``act(skip + bn(x))`` for mode "skipsum" / SKIP_SUM, ``act(cat((skip, bn(x)), 1))`` for "skipconcat" / SKIP_CONCAT,
-    with act = ReLU (``relu=True``), nothing (``relu=False``) or a callable ``act``.
+    with act = ReLU (``relu=True``), nothing (``relu=False``) or an activation module / callable ``act``.
 
     `bn` is a ``torch.nn.BatchNorm1d`` or this module's BatchNorm1d; its parameters are used and its running statistics
-    updated exactly as its own forward would.  With batch statistics on fp32 device tensors and ReLU or no activation
-    this is one engine op (mp::bn_skip_act: statistics, then one pass that normalises, adds or places the skip operand
-    and activates); everything else — eval mode with running statistics, CPU tensors, bf16, a single row, another
-    activation, a BatchNorm that carries its own fused ReLU — is the torch composition, the rule of BatchNorm1d.forward."""
+    updated exactly as its own forward would.  With batch statistics on fp32 device tensors this is one engine op:
+    mp::bn_skip_act for ReLU or no activation (``act=None``), mp::bn_skip_actx for an ``act`` module that act_spec
+    knows (statistics, then one pass that normalises, adds or places the skip operand and activates); everything
+    else — eval mode with running statistics, CPU tensors, bf16, a single row, an activation without a spec, a
+    BatchNorm that carries its own fused ReLU — is the torch composition, the rule of BatchNorm1d.forward."""
     mode = _SKIP_MODES[mode]
     _check_skip_shapes(x, skip, mode)
-    use_batch_stats = bn.training or not bn.track_running_stats
-    if not (act is None and isinstance(bn, nn.BatchNorm1d) and not getattr(bn, "relu", False) and use_batch_stats
-            and x.is_cuda and skip.is_cuda and x.size(0) > 1 and x.dtype != torch.bfloat16
+    spec = None if act is None else act_spec(act)
+    if not ((act is None or spec is not None) and _bn_on_engine(bn, x) and skip.is_cuda
             and skip.dtype != torch.bfloat16):
         y = bn(x)
         z = skip + y if mode == SKIP_SUM else torch.cat((skip, y), 1)
         return act(z) if act is not None else (torch.relu(z) if relu else z)
-    out, mean, _, var_u = torch.ops.mp.bn_skip_act(x, skip, bn.weight, bn.bias, float(bn.eps), bool(relu), mode)
+    if spec is None:
+        out, mean, _, var_u = torch.ops.mp.bn_skip_act(x, skip, bn.weight, bn.bias, float(bn.eps), bool(relu), mode)
+    else:
+        slope, param = _spec_args(spec)
+        out, mean, _, var_u = torch.ops.mp.bn_skip_actx(x, skip, bn.weight, bn.bias, slope, float(bn.eps), spec[0],
+                                                        param, mode)
     _update_running_stats(bn, mean, var_u)
     return out
 

@@ -344,6 +344,53 @@ int mp_bn_train_bwd_skip_f32(const float* dy, int64_t lddy, const float* out, in
                              float* dx, int64_t lddx, float* dskip, int64_t lddskip, float* dgamma, float* dbeta,
                              void* ws, size_t ws_bytes, mp_stream_t stream);
 
+/* The four passes above with ANY activation of GraphGym's act_dict (graphgym/models/act.py:6-14) or SiLU.  On the fp32
+ * pre-activation z (the BN term, plus skip in SUM; skip itself in CONCAT's left slab):
+ *   MP_ACT_NONE   z                                          MP_ACT_RELU   z > 0 ? z : 0
+ *   MP_ACT_LRELU  z > 0 ? z : act_param * z                  MP_ACT_PRELU  z > 0 ? z : slope[0] * z
+ *   MP_ACT_ELU    z > 0 ? z : act_param * expm1(z)           MP_ACT_SELU   scale * ELU_alpha(z), torch's two constants
+ *   MP_ACT_SILU   z * sigmoid(z)
+ * act_param: LRELU's negative slope / ELU's alpha (ignored otherwise).  slope: DEVICE pointer to PRELU's one fp32
+ * slope (nn.PReLU()), read by the kernels and never on the host; NULL for the other kinds.
+ *   fwd: the statistics and finalize launches of mp_bn_train_fwd_f32 / _skip_f32, then one apply launch; with NONE or
+ *        RELU the output has those entries' bits.
+ *   bwd: never reads the forward's output: z is recomputed from x, mean, invstd, gamma, beta (and skip) with the
+ *        forward's own expression, as mp_bn_train_bwd_relu_f32 recomputes its mask; g = dy * act'(z), then as above.
+ *        SUM: the statistics pass writes g to dskip and the apply pass reads it (7 N d); dskip NULL = not asked for,
+ *        the apply pass recomputes g.  CONCAT: dskip = dy[:, :d_skip] * act'(skip) in a launch of its own.  NONE:
+ *        dskip is not written (d(skip) is dy itself).
+ *        PRELU: dslope[0] = sum dy * min(z, 0) over every element the slope touched (CONCAT: both slabs) — one partial
+ *        per workgroup, added in double in a fixed order, no atomics; dslope NULL = not asked for.  The other kinds
+ *        neither compute nor store it.
+ * Unknown kind, PRELU without slope, or a skip shape that does not fit: MP_ERR_INVALID_ARG before any launch.
+ * The workspace is mp_bn_act_ws_bytes' (mp_bn_ws_bytes keeps its value). */
+#define MP_ACT_NONE 0
+#define MP_ACT_RELU 1
+#define MP_ACT_LRELU 2
+#define MP_ACT_PRELU 3
+#define MP_ACT_ELU 4
+#define MP_ACT_SELU 5
+#define MP_ACT_SILU 6
+int mp_bn_act_ws_bytes(int64_t N, int32_t d, size_t* bytes_host);
+int mp_bn_train_fwd_act_f32(const float* x, int64_t ldx, int64_t N, int32_t d, const float* gamma, const float* beta,
+                            float eps, int act, float act_param, const float* slope, float* y, int64_t ldy,
+                            float* mean, float* invstd, float* var_unbiased, void* ws, size_t ws_bytes,
+                            mp_stream_t stream);
+int mp_bn_train_bwd_act_f32(const float* dy, int64_t lddy, const float* x, int64_t ldx, int64_t N, int32_t d,
+                            const float* gamma, const float* beta, const float* mean, const float* invstd, int act,
+                            float act_param, const float* slope, float* dx, int64_t lddx, float* dgamma, float* dbeta,
+                            float* dslope, void* ws, size_t ws_bytes, mp_stream_t stream);
+int mp_bn_train_fwd_skip_act_f32(const float* x, int64_t ldx, const float* skip, int64_t ldskip, int64_t N, int32_t d,
+                                 int32_t d_skip, int mode, const float* gamma, const float* beta, float eps, int act,
+                                 float act_param, const float* slope, float* out, int64_t ldo, float* mean,
+                                 float* invstd, float* var_unbiased, void* ws, size_t ws_bytes, mp_stream_t stream);
+int mp_bn_train_bwd_skip_act_f32(const float* dy, int64_t lddy, const float* x, int64_t ldx, const float* skip,
+                                 int64_t ldskip, int64_t N, int32_t d, int32_t d_skip, int mode, const float* gamma,
+                                 const float* beta, const float* mean, const float* invstd, int act, float act_param,
+                                 const float* slope, float* dx, int64_t lddx, float* dskip, int64_t lddskip,
+                                 float* dgamma, float* dbeta, float* dslope, void* ws, size_t ws_bytes,
+                                 mp_stream_t stream);
+
 /* ------------------------------------------------------------------ *
  * Aggregate -> transform in one kernel                                *
  * ------------------------------------------------------------------ */
