@@ -20,6 +20,7 @@ ACT_NONE, ACT_RELU = 0, 1
 _p = C.c_void_p
 _i64 = C.c_int64
 _i32 = C.c_int32
+_u64 = C.c_uint64
 _f32 = C.c_float
 _sz = C.c_size_t
 _psz = C.POINTER(C.c_size_t)
@@ -81,6 +82,17 @@ PROTOTYPES = {
                                                _p, _p, _i64, _p, _p, _p, _p, _sz, _p]),
     "mp_bn_train_bwd_skip_act_f32": (C.c_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _i32, _i32, C.c_int, _p, _p, _p, _p,
                                                C.c_int, _f32, _p, _p, _i64, _p, _i64, _p, _p, _p, _p, _sz, _p]),
+    "mp_bn_drop_ws_bytes": (C.c_int, [_i64, _i32, _psz]),
+    "mp_bn_train_fwd_drop_act_f32": (C.c_int, [_p, _i64, _i64, _i32, _p, _p, _f32, C.c_int, _f32, _p, _i32, _u64, _u64, _p,
+                                               _i64, _p, _p, _p, _p, _sz, _p]),
+    "mp_bn_train_bwd_drop_act_f32": (C.c_int, [_p, _i64, _p, _i64, _i64, _i32, _p, _p, _p, _p, C.c_int, _f32, _p, _i32,
+                                               _u64, _u64, _p, _i64, _p, _p, _p, _p, _sz, _p]),
+    "mp_bn_train_fwd_drop_skip_act_f32": (C.c_int, [_p, _i64, _p, _i64, _i64, _i32, _i32, C.c_int, _p, _p, _f32, C.c_int,
+                                                    _f32, _p, _i32, _u64, _u64, _p, _i64, _p, _p, _p, _p, _sz, _p]),
+    "mp_bn_train_bwd_drop_skip_act_f32": (C.c_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _i32, _i32, C.c_int, _p, _p, _p,
+                                                    _p, C.c_int, _f32, _p, _i32, _u64, _u64, _p, _i64, _p, _i64, _p, _p,
+                                                    _p, _p, _sz, _p]),
+    "mp_dropout_keyed_f32": (C.c_int, [_p, _i64, _i64, _i32, _i32, _u64, _u64, _p, _i64, _p]),
     "mp_agg_rows_tiles_f32": (C.c_int, [_p, _p, _p, _i64, C.c_int, _p, _i64, _i32, _p, _i64, C.c_float, _p, _i64, _p]),
     "mp_agg_rows_tiles_hot_f32": (C.c_int, [_p, _p, _p, _i64, C.c_int, _p, _i64, _i32, _p, _i64, C.c_float, _p, _i64, _p]),
     "mp_agg_dense_f32": (C.c_int, [_p, _p, _p, _i64, C.c_int, _p, _i64, _i32, _p, _i64, C.c_float, _p, _i64, _i32, _p, C.c_int,

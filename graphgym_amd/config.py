@@ -32,7 +32,8 @@ def _defaults():
         self_msg="concat", att_heads=1, l2norm=True,
         msg_direction="single", keep_edge=0.5,
         att_final_linear=False, att_final_linear_bn=False,
-        skip_every=1)                                                     # config.py:313-372 (:363-366, :331)
+        skip_every=1,                                                     # config.py:313-372 (:363-366, :331)
+        keyed_dropout=False)              # ours: gnn.dropout through graphgym_amd.nn.Dropout, fused into the BatchNorm passes
     cfg.bn = types.SimpleNamespace(eps=1e-5, mom=0.1)                     # config.py:409-412
     cfg.mem = types.SimpleNamespace(inplace=False)                        # config.py:420
     cfg.optim = types.SimpleNamespace(base_lr=0.01, max_epoch=200, weight_decay=5e-4)

@@ -17,43 +17,14 @@
 // Column sums are accumulated per workgroup over a contiguous run of rows (fp32, <= a few thousand terms
 // per lane), written as partial slabs and combined in double precision in slab order: deterministic and
 // accurate at 10^7 rows.
-#include "common.h"
-#include "vecio.h"
-#include "act.h"
+#include "bn_shared.h"
 
 namespace mp {
-
-constexpr int kBnMaxBlocks = kNumCU * 8;
-
-struct BnGeom {
-  int cg;        // column groups (threads along the feature axis), each owns W consecutive columns
-  int rl;        // rows processed in parallel by one workgroup
-  int tiles;     // column tiles when d > cg * W
-};
-
-template <int W>
-__host__ __device__ inline BnGeom bn_geom(int d) {
-  BnGeom g;
-  const int groups = (d + W - 1) / W;
-  g.cg = groups < kBlock ? groups : kBlock;
-  int p = 1;
-  while (p < g.cg) p <<= 1;             // power of two so that rl = 256 / cg is exact
-  g.cg = p > kBlock ? kBlock : p;
-  g.rl = kBlock / g.cg;
-  g.tiles = (groups + g.cg - 1) / g.cg;
-  return g;
-}
 
 // MODE 0: a = sum(x - pivot), b = sum((x - pivot)^2)          (forward statistics; pivot = bn_pivot(x))
 // MODE 1: a = sum(g),         b = sum(g * (x - pivot)),  g = dy * [y > 0] when y != nullptr, pivot = mean
 // MODE 2: MODE 1 with y given, and g written to gout on the way: the skip block's d(skip), which its apply pass then
 //         reads in place of dy and y
-// the affine scale of the apply pass, from the ROUNDED invstd the forward hands out: the forward and a backward that
-// recomputes the activation from x get the same bits
-__host__ __device__ __forceinline__ float bn_scale(float gamma, float invstd) {
-  return (float)((double)gamma * (double)invstd);
-}
-
 // The pivot of the forward statistics: per column the median of rows 0, N / 2 and N - 1.  The sums are taken of
 // x - pivot, and var = E[v^2] - E[v]^2 loses (pivot - mean)^2 / var of the fp32 partials' precision: a single sample is an
 // outlier too often — row 0 of a preferential-attachment graph is its largest hub, ten and more standard deviations
@@ -82,7 +53,6 @@ __global__ __launch_bounds__(kBlock) void bn_colsum_kernel(const float* __restri
   // mx_invstd != NULL (MODE 1): the ReLU mask [y > 0] is recomputed from x — y = relu(fmaf(x - mean, scale, beta))
   // with scale = float(gamma * invstd), the forward's own expression on the forward's own operands, bit for bit —
   // instead of reading y
-  __shared__ float red[2][kBlock][W];
   const BnGeom g = bn_geom<W>(d);
   const int cgi = threadIdx.x % g.cg;
   const int rli = threadIdx.x / g.cg;
@@ -141,57 +111,8 @@ __global__ __launch_bounds__(kBlock) void bn_colsum_kernel(const float* __restri
         }
       }
     }
-#pragma unroll
-    for (int k = 0; k < W; ++k) { red[0][threadIdx.x][k] = a[k]; red[1][threadIdx.x][k] = b[k]; }
-    __syncthreads();
-    if (rli == 0 && on) {
-#pragma unroll
-      for (int k = 0; k < W; ++k) {
-        float sa = 0.f, sb = 0.f;
-        for (int q = 0; q < g.rl; ++q) { sa += red[0][q * g.cg + cgi][k]; sb += red[1][q * g.cg + cgi][k]; }
-        if (c0 + k < d) {
-          partial[((int64_t)blockIdx.x * 2 + 0) * d + c0 + k] = sa;
-          partial[((int64_t)blockIdx.x * 2 + 1) * d + c0 + k] = sb;
-        }
-      }
-    }
-    __syncthreads();
+    bn_colsum_store<W>(a, b, g, cgi, rli, on, c0, d, partial);
   }
-}
-
-// The two column sums of a finalize kernel over the nblk per-block partials, in double and in a fixed order: a
-// workgroup owns 16 columns, its 16 block lanes each add every 16th partial through two independent running sums per
-// quantity, and lane 0 adds the 16 lane sums in lane order.  (One thread per column walking all partials in a dependent
-// chain of double adds took 0.8 ms per call at 2 048 partials.)  Returns true in the threads that hold a result.
-__device__ __forceinline__ bool bn_col_sums(const float* __restrict__ partial, int nblk, int32_t d, int& c, double& s1,
-                                            double& s2) {
-  __shared__ double part[2][16][16];
-  const int e = threadIdx.x & 15, sl = threadIdx.x >> 4;
-  c = blockIdx.x * 16 + e;
-  double a1 = 0.0, b1 = 0.0, a2 = 0.0, b2 = 0.0;
-  if (c < d) {
-    int b = sl;
-    for (; b + 16 < nblk; b += 32) {
-      a1 += (double)partial[((int64_t)b * 2 + 0) * d + c];
-      a2 += (double)partial[((int64_t)b * 2 + 1) * d + c];
-      b1 += (double)partial[((int64_t)(b + 16) * 2 + 0) * d + c];
-      b2 += (double)partial[((int64_t)(b + 16) * 2 + 1) * d + c];
-    }
-    if (b < nblk) {
-      a1 += (double)partial[((int64_t)b * 2 + 0) * d + c];
-      a2 += (double)partial[((int64_t)b * 2 + 1) * d + c];
-    }
-  }
-  part[0][sl][e] = a1 + b1;
-  part[1][sl][e] = a2 + b2;
-  __syncthreads();
-  s1 = 0.0; s2 = 0.0;
-  if (sl == 0 && c < d) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { s1 += part[0][r][e]; s2 += part[1][r][e]; }
-    return true;
-  }
-  return false;
 }
 
 // forward finalize: mean, invstd, unbiased variance, and the affine of the apply pass
@@ -352,36 +273,7 @@ __global__ __launch_bounds__(kBlock) void bn_apply_skip_kernel(const float* __re
 }
 
 // ---- the same passes with any activation of act.h ----------------------------------------------------------------------
-// ACT is a template parameter; `prm` is the kind's host parameter (LRELU's slope, ELU's alpha) and `slope` the device
-// pointer to PRELU's one learnable slope, read here and never on the host.
-template <int ACT>
-__device__ __forceinline__ float act_param(float prm, const float* __restrict__ slope) {
-  if constexpr (ACT == MP_ACT_PRELU) return slope[0];
-  else return prm;
-}
-
-// the sum of one value per thread over the workgroup, in double and in thread order: 16 threads add 16 values each,
-// thread 0 adds the 16 sums and stores
-__device__ __forceinline__ void bn_block_sum(float c, float* __restrict__ dst) {
-  __shared__ float v[kBlock];
-  __shared__ double w[16];
-  v[threadIdx.x] = c;
-  __syncthreads();
-  if (threadIdx.x < 16) {
-    double s = 0.0;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) s += (double)v[threadIdx.x * 16 + q];
-    w[threadIdx.x] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double s = 0.0;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) s += w[q];
-    *dst = (float)s;
-  }
-}
-
+// (act_param<ACT>: bn_shared.h)
 // forward apply: out = act((x - ctr) * p0 + p1), bn_apply_kernel<W, 0>'s fmaf
 template <int W, int ACT>
 __global__ __launch_bounds__(kBlock) void bn_apply_act_kernel(const float* __restrict__ x, int64_t ldx,
@@ -470,7 +362,6 @@ __global__ __launch_bounds__(kBlock) void bn_colsum_act_kernel(const float* __re
                                                                int64_t rows_per_block, float* __restrict__ partial,
                                                                float* __restrict__ partial3,
                                                                float* __restrict__ gout, int64_t ldg) {
-  __shared__ float red[2][kBlock][W];
   const float ap = act_param<ACT>(prm, slope);
   const BnGeom g = bn_geom<W>(d);
   const int cgi = threadIdx.x % g.cg;
@@ -517,21 +408,7 @@ __global__ __launch_bounds__(kBlock) void bn_colsum_act_kernel(const float* __re
         }
       }
     }
-#pragma unroll
-    for (int k = 0; k < W; ++k) { red[0][threadIdx.x][k] = a[k]; red[1][threadIdx.x][k] = b[k]; }
-    __syncthreads();
-    if (rli == 0 && on) {
-#pragma unroll
-      for (int k = 0; k < W; ++k) {
-        float sa = 0.f, sb = 0.f;
-        for (int q = 0; q < g.rl; ++q) { sa += red[0][q * g.cg + cgi][k]; sb += red[1][q * g.cg + cgi][k]; }
-        if (c0 + k < d) {
-          partial[((int64_t)blockIdx.x * 2 + 0) * d + c0 + k] = sa;
-          partial[((int64_t)blockIdx.x * 2 + 1) * d + c0 + k] = sb;
-        }
-      }
-    }
-    __syncthreads();
+    bn_colsum_store<W>(a, b, g, cgi, rli, on, c0, d, partial);
   }
   if (ACT == MP_ACT_PRELU) bn_block_sum(c3, partial3 + blockIdx.x);
 }
@@ -629,55 +506,45 @@ __global__ __launch_bounds__(kBlock) void bn_dslope_finalize_kernel(const float*
   }
 }
 
-static int bn_blocks(int64_t N) {
-  int64_t b = ceil_div(N, 64);
-  if (b < 1) b = 1;
-  if (b > kBnMaxBlocks) b = kBnMaxBlocks;
-  return (int)b;
-}
-
-static bool bn_al(const void* p, size_t a) { return p == nullptr || ((uintptr_t)p % a) == 0; }
-
-struct BnWs { float* partial; float* v[5]; size_t total; };
-static void bn_ws_layout(int64_t N, int32_t d, void* base, BnWs* w) {
-  char* p = (char*)base;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { void* r = p ? p + off : nullptr; off += align_up(bytes, 256); return r; };
-  w->partial = (float*)take((size_t)bn_blocks(N) * 2 * d * 4);
-  for (int i = 0; i < 5; ++i) w->v[i] = (float*)take((size_t)d * 4);
-  w->total = off;
-}
-
-// the workspace of the *_act entries: mp_bn_ws_bytes' layout, then PRELU's per-workgroup sums (the BN slab's, then the
-// CONCAT left slab's)
-struct BnActWs { BnWs bn; float* partial3; size_t total; };
-static void bn_act_ws_layout(int64_t N, int32_t d, void* base, BnActWs* w) {
-  bn_ws_layout(N, d, base, &w->bn);
-  w->partial3 = base ? (float*)((char*)base + w->bn.total) : nullptr;
-  w->total = w->bn.total + align_up((size_t)2 * kBnMaxBlocks * 4, 256);
-}
-
-static bool act_known(int act) { return act >= MP_ACT_NONE && act <= MP_ACT_SILU; }
-
-}  // namespace mp
-
-using namespace mp;
-
-extern "C" {
-
-int mp_bn_ws_bytes(int64_t N, int32_t d, size_t* bytes_host) {
-  if (!bytes_host || N < 0 || d <= 0) return MP_ERR_INVALID_ARG;
-  BnWs w;
-  bn_ws_layout(N, d, nullptr, &w);
-  *bytes_host = w.total;
+// ---- the launches bn_drop.hip shares (declared in bn_shared.h) ----------------------------------------------------------
+int bn_bwd_finalize(int64_t N, int32_t d, const float* gamma, const float* mean, const float* invstd, float* dgamma,
+                    float* dbeta, const BnWs& L, int nslab, bool fwd_scale, hipStream_t st) {
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)ceil_div(d, 16)), dim3(kBlock), 0, st, L.partial,
+                     nslab, N, d, gamma, mean, invstd, dgamma, dbeta, L.v[0], L.v[1], L.v[2],
+                     fwd_scale ? L.v[3] : nullptr);
+  MP_LAUNCH_CHECK();
   return MP_OK;
 }
 
-// the statistics and finalize launches of the forward: mean / invstd / var_unbiased, and the affine of the apply pass in
-// L.v[0] (scale) and L.v[1] (shift)
-static int bn_fwd_stats(const float* x, int64_t ldx, int64_t N, int32_t d, const float* gamma, const float* beta,
-                        float eps, float* mean, float* invstd, float* var_unbiased, const BnWs& L, bool vec,
-                        hipStream_t st) {
+int bn_dslope_finalize(const BnActWs& L, int n, float* dslope, hipStream_t st) {
+  hipLaunchKernelGGL(bn_dslope_finalize_kernel, dim3(1), dim3(kBlock), 0, st, L.partial3, n, dslope);
+  MP_LAUNCH_CHECK();
+  return MP_OK;
+}
+
+int bn_act_bwd_left(int act, const float* dy, int64_t lddy, const float* skip, int64_t ldskip, float prm,
+                    const float* slope, int64_t N, int32_t d_skip, float* dskip, int64_t lddskip, const BnActWs& L,
+                    hipStream_t st) {
+  const int nblk = bn_blocks(N);
+  const int64_t rpb = ceil_div(N, nblk);
+  const bool vl = d_skip % 4 == 0 && lddy % 4 == 0 && ldskip % 4 == 0 && bn_al(dy, 16) && bn_al(skip, 16) &&
+                  (!dskip || (lddskip % 4 == 0 && bn_al(dskip, 16)));
+  const bool known = with_act(act, [&](auto a) {
+    constexpr int A = decltype(a)::value;
+    if (vl)
+      hipLaunchKernelGGL((bn_act_bwd_left_kernel<4, A>), dim3(nblk), dim3(kBlock), 0, st, dy, lddy, skip, ldskip, prm,
+                         slope, N, d_skip, rpb, dskip, lddskip, L.partial3 + nblk);
+    else
+      hipLaunchKernelGGL((bn_act_bwd_left_kernel<1, A>), dim3(nblk), dim3(kBlock), 0, st, dy, lddy, skip, ldskip, prm,
+                         slope, N, d_skip, rpb, dskip, lddskip, L.partial3 + nblk);
+  });
+  if (!known) return MP_ERR_INVALID_ARG;
+  MP_LAUNCH_CHECK();
+  return MP_OK;
+}
+
+int bn_fwd_stats(const float* x, int64_t ldx, int64_t N, int32_t d, const float* gamma, const float* beta, float eps,
+                 float* mean, float* invstd, float* var_unbiased, const BnWs& L, bool vec, hipStream_t st) {
   const int nblk = bn_blocks(N);
   const int64_t rpb = ceil_div(N, nblk);
   if (vec)       // the sums are shifted by bn_pivot(x), which both kernels take from x themselves
@@ -690,6 +557,20 @@ static int bn_fwd_stats(const float* x, int64_t ldx, int64_t N, int32_t d, const
   hipLaunchKernelGGL(bn_fwd_finalize_kernel, dim3((unsigned)ceil_div(d, 16)), dim3(kBlock), 0, st, L.partial, nblk,
                      x, ldx, N, d, gamma, beta, eps, mean, invstd, var_unbiased, L.v[0], L.v[1]);
   MP_LAUNCH_CHECK();
+  return MP_OK;
+}
+
+}  // namespace mp
+
+using namespace mp;
+
+extern "C" {
+
+int mp_bn_ws_bytes(int64_t N, int32_t d, size_t* bytes_host) {
+  if (!bytes_host || N < 0 || d <= 0) return MP_ERR_INVALID_ARG;
+  BnWs w;
+  bn_ws_layout(N, d, nullptr, &w);
+  *bytes_host = w.total;
   return MP_OK;
 }
 
@@ -788,9 +669,8 @@ static int bn_bwd_common(const float* dy, int64_t lddy, const float* y, int64_t 
     hipLaunchKernelGGL((bn_colsum_kernel<1, 1>), dim3(nblk), dim3(kBlock), 0, st, x, ldx, dy, lddy, y, ldy, mean, N,
                        d, rpb, L.partial, mg, mb, mi);
   MP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)ceil_div(d, 16)), dim3(kBlock), 0, st, L.partial, nblk,
-                     N, d, gamma, mean, invstd, dgamma, dbeta, L.v[0], L.v[1], L.v[2], mask_from_x ? L.v[3] : nullptr);
-  MP_LAUNCH_CHECK();
+  const int rc = bn_bwd_finalize(N, d, gamma, mean, invstd, dgamma, dbeta, L, nblk, mask_from_x != 0, st);
+  if (rc != MP_OK) return rc;
   const float* msc = mask_from_x ? L.v[3] : nullptr;
   if (dskip) { dy = dskip; lddy = lddskip; y = nullptr; }     // g is on hand: the mask is already applied
   if (vec)
@@ -942,9 +822,8 @@ static int bn_bwd_act_launch(const float* dy, int64_t lddy, const float* x, int6
     hipLaunchKernelGGL((bn_colsum_act_kernel<1, ACT>), dim3(nblk), dim3(kBlock), 0, st, x, ldx, dy, lddy, skip, ldskip,
                        mean, gamma, beta, invstd, prm, slope, N, d, rpb, B.partial, L.partial3, gout, ldg);
   MP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)ceil_div(d, 16)), dim3(kBlock), 0, st, B.partial, nblk, N,
-                     d, gamma, mean, invstd, dgamma, dbeta, B.v[0], B.v[1], B.v[2], B.v[3]);
-  MP_LAUNCH_CHECK();
+  const int rc = bn_bwd_finalize(N, d, gamma, mean, invstd, dgamma, dbeta, B, nblk, true, st);
+  if (rc != MP_OK) return rc;
   if (gout != nullptr) {      // g is on hand
     if (vec)
       hipLaunchKernelGGL((bn_apply_kernel<4, 1>), dim3(flat_grid(N * (d / 4))), dim3(kBlock), 0, st, x, ldx, gout, ldg,
@@ -959,12 +838,6 @@ static int bn_bwd_act_launch(const float* dy, int64_t lddy, const float* x, int6
     hipLaunchKernelGGL((bn_apply_bwd_act_kernel<1, ACT>), dim3(flat_grid(N * d)), dim3(kBlock), 0, st, x, ldx, dy, lddy,
                        skip, ldskip, B.v[0], B.v[1], B.v[2], mean, B.v[3], beta, prm, slope, N, d, dx, lddx);
   }
-  MP_LAUNCH_CHECK();
-  return MP_OK;
-}
-
-static int bn_dslope_finalize(const BnActWs& L, int n, float* dslope, hipStream_t st) {
-  hipLaunchKernelGGL(bn_dslope_finalize_kernel, dim3(1), dim3(kBlock), 0, st, L.partial3, n, dslope);
   MP_LAUNCH_CHECK();
   return MP_OK;
 }
@@ -1018,25 +891,18 @@ int mp_bn_train_bwd_skip_act_f32(const float* dy, int64_t lddy, const float* x, 
                          ws, ws_bytes, st);
   const int nblk = bn_blocks(N);
   const bool left = cat && (dskip || (act == MP_ACT_PRELU && dslope));
-  const bool vl = d_skip % 4 == 0 && lddy % 4 == 0 && ldskip % 4 == 0 && bn_al(dy, 16) && bn_al(skip, 16) &&
-                  (!dskip || (lddskip % 4 == 0 && bn_al(dskip, 16)));
   int rc = MP_OK;
   with_act(act, [&](auto a) {
     constexpr int A = decltype(a)::value;
     rc = bn_bwd_act_launch<A>(dyr, lddy, x, ldx, cat ? nullptr : skip, cat ? 0 : ldskip, N, d, gamma, beta, mean, invstd,
                               act_param, slope, dx, lddx, cat ? nullptr : dskip, cat ? 0 : lddskip, dgamma, dbeta, L,
                               st);
-    if (rc != MP_OK || !left) return;
-    const int64_t rpb = ceil_div(N, nblk);
-    if (vl)
-      hipLaunchKernelGGL((bn_act_bwd_left_kernel<4, A>), dim3(nblk), dim3(kBlock), 0, st, dy, lddy, skip, ldskip,
-                         act_param, slope, N, d_skip, rpb, dskip, lddskip, L.partial3 + nblk);
-    else
-      hipLaunchKernelGGL((bn_act_bwd_left_kernel<1, A>), dim3(nblk), dim3(kBlock), 0, st, dy, lddy, skip, ldskip,
-                         act_param, slope, N, d_skip, rpb, dskip, lddskip, L.partial3 + nblk);
   });
   if (rc != MP_OK) return rc;
-  MP_LAUNCH_CHECK();
+  if (left) {
+    rc = bn_act_bwd_left(act, dy, lddy, skip, ldskip, act_param, slope, N, d_skip, dskip, lddskip, L, st);
+    if (rc != MP_OK) return rc;
+  }
   if (act == MP_ACT_PRELU && dslope) return bn_dslope_finalize(L, cat ? 2 * nblk : nblk, dslope, st);
   return MP_OK;
 }

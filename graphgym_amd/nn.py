@@ -6,10 +6,13 @@ names (weight, bias, running_mean, running_var, num_batches_tracked), same momen
 training mode the statistics, the normalisation, the optional ReLU and the whole backward run as four
 HBM-bound passes; torch's own kernel needs 0.5 s per backward call on a [10^7, 256] activation.  Any other activation
 of GraphGym's act_dict (and SiLU) rides the same passes through bn_act_module / bn_skip_act(act=...): act_spec says which.
+gnn.dropout between the BatchNorm and the activation rides them too, as a keyed mask that is recomputed and never stored:
+Dropout, dropout_keep_host, bn_act_module / bn_skip_act(drop=...) (csrc/draws.h, csrc/bn_drop.hip).
 """
 import ctypes as C
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -557,6 +560,330 @@ def _bn_skip_actx_backward(ctx, dy, _dmean, _dinvstd, _dvar):
 register_autograd("mp::bn_skip_actx", _bn_skip_actx_backward, setup_context=_bn_skip_actx_setup)
 
 
+# ---- gnn.dropout between the BatchNorm and the activation: a keyed mask (csrc/draws.h, csrc/bn_drop.hip) -------------
+# The mask is a pure function of (seed, offset, row, column): nothing is stored, the backward recomputes it.  Its
+# definition is the comment in csrc/draws.h; dropout_keep_host restates it in NumPy integers, bit for bit.
+_M64 = (1 << 64) - 1
+_GOLDEN = 0x9E3779B97F4A7C15
+DROP_ONE = 65536                        # a rate is T / 65536
+
+
+def dropout_threshold(p):
+    """T = round(p * 65536) in [0, 65536]: an element is kept iff its 16-bit draw is >= T"""
+    p = float(p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"dropout probability has to be between 0 and 1, but got {p}")
+    return int(p * DROP_ONE + 0.5)
+
+
+def dropout_scale(p):
+    """the fp32 factor of the kept elements, 1 / (1 - T / 65536) rounded once; 0 when everything is dropped"""
+    T = dropout_threshold(p)
+    return 0.0 if T == DROP_ONE else float(np.float32(65536.0 / (DROP_ONE - T)))
+
+
+def _mix64(z):
+    """draws.h mix64 on a uint64 array (wrapping arithmetic)"""
+    with np.errstate(over="ignore"):
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return z ^ (z >> np.uint64(31))
+
+
+def dropout_keep_host(seed, offset, N, d, p):
+    """keep(seed, offset, r, c) of csrc/draws.h over an [N, d] operand on the host: bool tensor [N, d] on the CPU (NumPy
+    integers, no device).  One hash per aligned group of four columns; column c takes its 16-bit lane c % 4."""
+    T = dropout_threshold(p)
+    g = np.uint64(_GOLDEN)
+    q = (d + 3) // 4
+    with np.errstate(over="ignore"):
+        key = _mix64(np.asarray(int(seed) & _M64, dtype=np.uint64) + g)
+        key = _mix64((key ^ np.uint64(int(offset) & _M64)) + g)
+        group = (np.arange(N, dtype=np.uint64)[:, None] * np.uint64(q) + np.arange(q, dtype=np.uint64)[None, :])
+        h = _mix64((key ^ group) + g)                                    # [N, q]
+    lanes = (h[:, :, None] >> (np.uint64(16) * np.arange(4, dtype=np.uint64))) & np.uint64(0xFFFF)
+    keep = lanes.reshape(N, 4 * q)[:, :d] >= np.uint64(T)
+    return torch.from_numpy(np.ascontiguousarray(keep))
+
+
+def _drop_args(T, seed, offset):
+    if not 0 <= T <= DROP_ONE:
+        raise ValueError(f"the dropout threshold must lie in [0, {DROP_ONE}], got {T}")
+    return int(T), C.c_uint64(int(seed) & _M64), C.c_uint64(int(offset) & _M64)
+
+
+@custom_op("mp::dropout_keyed", mutates_args=(), device_types="cuda")
+def _op_dropout_keyed(x: Tensor, T: int, seed: int, offset: int) -> Tensor:
+    """out = keep(seed, offset) * scale * x over an [N, d] fp32 view; kept iff the element's draw is >= T"""
+    _require_hip(x, "x")
+    if x.dim() != 2:
+        raise ValueError(f"dropout_keyed takes [N, d], got {tuple(x.shape)}")
+    T, seed_c, off_c = _drop_args(T, seed, offset)
+    x = _rows32(x)
+    N, d = x.shape
+    out = placement.empty_or_torch((N, d), x.device, reads=(x,), streaming=True)
+    if N == 0 or d == 0:
+        return out
+    with torch.cuda.device(x.device):
+        check(lib().mp_dropout_keyed_f32(ptr(x), x.stride(0), N, d, T, seed_c, off_c, ptr(out), out.stride(0),
+                                         _stream()), "mp_dropout_keyed_f32")
+    return out
+
+
+@_op_dropout_keyed.register_fake
+def _(x, T, seed, offset):
+    return x.new_empty(x.shape, dtype=torch.float32)
+
+
+def _dropout_keyed_setup(ctx, inputs, output):
+    _, ctx.T, ctx.seed, ctx.offset = inputs
+
+
+def _dropout_keyed_backward(ctx, dy):
+    # the same launch on dy: the mask is recomputed from the key
+    return torch.ops.mp.dropout_keyed(dy, ctx.T, ctx.seed, ctx.offset), None, None, None
+
+
+register_autograd("mp::dropout_keyed", _dropout_keyed_backward, setup_context=_dropout_keyed_setup)
+
+
+def _bn_drop_ws(N, d, device):
+    nb = C.c_size_t(0)
+    check(lib().mp_bn_drop_ws_bytes(N, d, C.byref(nb)))
+    return torch.empty(nb.value, dtype=torch.uint8, device=device), nb.value
+
+
+@custom_op("mp::bn_drop_actx_fwd_raw", mutates_args=(), device_types="cuda")
+def _op_bn_drop_actx_fwd_raw(x: Tensor, weight: Optional[Tensor], bias: Optional[Tensor], slope: Optional[Tensor],
+                             eps: float, kind: int, param: float, T: int, seed: int,
+                             offset: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(y, mean, invstd, unbiased var): y = act(keep * scale * BatchNorm1d(x)) with batch statistics"""
+    _require_hip(x, "x")
+    _check_kind(kind, slope)
+    T, seed_c, off_c = _drop_args(T, seed, offset)
+    x = _rows32(x)
+    N, d = x.shape
+    y = placement.empty_or_torch((N, d), x.device, reads=(x,), streaming=True)
+    mean = torch.empty(d, dtype=torch.float32, device=x.device)
+    invstd = torch.empty_like(mean)
+    var_u = torch.empty_like(mean)
+    w = None if weight is None else weight.detach().contiguous()
+    b = None if bias is None else bias.detach().contiguous()
+    s = _slope32(slope, kind)
+    with torch.cuda.device(x.device):
+        ws, nb = _bn_drop_ws(N, d, x.device)
+        check(lib().mp_bn_train_fwd_drop_act_f32(ptr(x), x.stride(0), N, d, ptr(w), ptr(b), float(eps), kind,
+                                                 float(param), ptr(s), T, seed_c, off_c, ptr(y), y.stride(0), ptr(mean),
+                                                 ptr(invstd), ptr(var_u), ptr(ws), nb, _stream()),
+              "mp_bn_train_fwd_drop_act_f32")
+    return y, mean, invstd, var_u
+
+
+@_op_bn_drop_actx_fwd_raw.register_fake
+def _(x, weight, bias, slope, eps, kind, param, T, seed, offset):
+    return (x.new_empty(x.shape, dtype=torch.float32),) + _stats_fake(x)
+
+
+@custom_op("mp::bn_drop_actx_bwd_raw", mutates_args=(), device_types="cuda")
+def _op_bn_drop_actx_bwd_raw(dy: Tensor, x: Tensor, weight: Optional[Tensor], bias: Optional[Tensor],
+                             slope: Optional[Tensor], mean: Tensor, invstd: Tensor, kind: int, param: float, T: int,
+                             seed: int, offset: int,
+                             want_dslope: bool = True) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(dx, dgamma, dbeta, dslope) of bn_drop_actx_fwd_raw.  Neither the forward's output nor a mask is an operand: the
+    masked pre-activation is recomputed from x, the statistics and the key.  dslope as in bn_actx_bwd_raw."""
+    _check_kind(kind, slope)
+    T, seed_c, off_c = _drop_args(T, seed, offset)
+    x, dy = _rows32(x), _rows32(dy)
+    N, d = x.shape
+    dx = placement.empty_or_torch((N, d), x.device, reads=(dy, x), streaming=True)
+    dgamma = torch.empty(d, dtype=torch.float32, device=x.device)
+    dbeta = torch.empty_like(dgamma)
+    dslope = torch.empty(1 if (kind == ACT_PRELU and want_dslope) else 0, dtype=torch.float32, device=x.device)
+    w = None if weight is None else weight.detach().contiguous()
+    b = None if bias is None else bias.detach().contiguous()
+    s = _slope32(slope, kind)
+    with torch.cuda.device(x.device):
+        ws, nb = _bn_drop_ws(N, d, x.device)
+        check(lib().mp_bn_train_bwd_drop_act_f32(ptr(dy), dy.stride(0), ptr(x), x.stride(0), N, d, ptr(w), ptr(b),
+                                                 ptr(mean), ptr(invstd), kind, float(param), ptr(s), T, seed_c, off_c,
+                                                 ptr(dx), dx.stride(0), ptr(dgamma), ptr(dbeta),
+                                                 ptr(dslope) if dslope.numel() else None, ptr(ws), nb, _stream()),
+              "mp_bn_train_bwd_drop_act_f32")
+    return dx, dgamma, dbeta, dslope
+
+
+@_op_bn_drop_actx_bwd_raw.register_fake
+def _(dy, x, weight, bias, slope, mean, invstd, kind, param, T, seed, offset, want_dslope=True):
+    return (x.new_empty(x.shape, dtype=torch.float32),) + _stats_fake(x)[:2] + (
+        x.new_empty((1 if (kind == ACT_PRELU and want_dslope) else 0,), dtype=torch.float32),)
+
+
+@custom_op("mp::bn_drop_actx", mutates_args=(), device_types="cuda")
+def _op_bn_drop_actx(x: Tensor, weight: Optional[Tensor], bias: Optional[Tensor], slope: Optional[Tensor], eps: float,
+                     kind: int, param: float, T: int, seed: int,
+                     offset: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """graphgym/models/layer.py:26-35 (BatchNorm1d, Dropout, cfg.gnn.act) in training mode with the keyed mask of
+    (T, seed, offset): (y, mean, invstd, var)"""
+    return torch.ops.mp.bn_drop_actx_fwd_raw(x, weight, bias, slope, eps, kind, param, T, seed, offset)
+
+
+@_op_bn_drop_actx.register_fake
+def _(x, weight, bias, slope, eps, kind, param, T, seed, offset):
+    return (x.new_empty(x.shape, dtype=torch.float32),) + _stats_fake(x)
+
+
+def _bn_drop_actx_setup(ctx, inputs, output):
+    x, weight, bias, slope, eps, kind, param, T, seed, offset = inputs
+    _, mean, invstd, _ = output
+    ctx.kind, ctx.param, ctx.drop = kind, param, (T, seed, offset)
+    ctx.has = (weight is not None, bias is not None, slope is not None)
+    ctx.slope_shape = None if slope is None else slope.shape
+    ctx.save_for_backward(x, weight, bias, slope, mean, invstd)      # neither y nor a mask: both are recomputed
+
+
+def _bn_drop_actx_backward(ctx, dy, _dmean, _dinvstd, _dvar):
+    x, w, b, s, mean, invstd = ctx.saved_tensors
+    need_x, need_w, need_b, need_s = ctx.needs_input_grad[:4]
+    need_s = need_s and ctx.kind == ACT_PRELU
+    if not (need_x or need_w or need_b or need_s):
+        return (None,) * 10
+    dx, dgamma, dbeta, dslope = torch.ops.mp.bn_drop_actx_bwd_raw(dy, x, w, b, s, mean, invstd, ctx.kind, ctx.param,
+                                                                  *ctx.drop, need_s)
+    return (dx if need_x else None, dgamma if (need_w and ctx.has[0]) else None,
+            dbeta if (need_b and ctx.has[1]) else None, dslope.reshape(ctx.slope_shape) if need_s else None,
+            None, None, None, None, None, None)
+
+
+register_autograd("mp::bn_drop_actx", _bn_drop_actx_backward, setup_context=_bn_drop_actx_setup)
+
+
+@custom_op("mp::bn_drop_skip_actx_fwd_raw", mutates_args=(), device_types="cuda")
+def _op_bn_drop_skip_actx_fwd_raw(x: Tensor, skip: Tensor, weight: Optional[Tensor], bias: Optional[Tensor],
+                                  slope: Optional[Tensor], eps: float, kind: int, param: float, mode: int, T: int,
+                                  seed: int, offset: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """bn_skip_actx_fwd_raw with the keyed mask on the BatchNorm term, before the skip operand"""
+    _require_hip(x, "x")
+    _require_hip(skip, "skip")
+    _check_skip_shapes(x, skip, mode)
+    _check_kind(kind, slope)
+    T, seed_c, off_c = _drop_args(T, seed, offset)
+    x, skip = _rows32(x), _rows32(skip)
+    N, d = x.shape
+    d_skip = skip.size(1)
+    out = placement.empty_or_torch((N, d if mode == SKIP_SUM else d_skip + d), x.device, reads=(x, skip),
+                                   streaming=True)
+    mean = torch.empty(d, dtype=torch.float32, device=x.device)
+    invstd = torch.empty_like(mean)
+    var_u = torch.empty_like(mean)
+    w = None if weight is None else weight.detach().contiguous()
+    b = None if bias is None else bias.detach().contiguous()
+    s = _slope32(slope, kind)
+    with torch.cuda.device(x.device):
+        ws, nb = _bn_drop_ws(N, d, x.device)
+        check(lib().mp_bn_train_fwd_drop_skip_act_f32(ptr(x), x.stride(0), ptr(skip), skip.stride(0), N, d, d_skip, mode,
+                                                      ptr(w), ptr(b), float(eps), kind, float(param), ptr(s), T, seed_c,
+                                                      off_c, ptr(out), out.stride(0), ptr(mean), ptr(invstd),
+                                                      ptr(var_u), ptr(ws), nb, _stream()),
+              "mp_bn_train_fwd_drop_skip_act_f32")
+    return out, mean, invstd, var_u
+
+
+@_op_bn_drop_skip_actx_fwd_raw.register_fake
+def _(x, skip, weight, bias, slope, eps, kind, param, mode, T, seed, offset):
+    return _skip_fake(x, skip, mode)
+
+
+@custom_op("mp::bn_drop_skip_actx_bwd_raw", mutates_args=(), device_types="cuda")
+def _op_bn_drop_skip_actx_bwd_raw(dy: Tensor, x: Tensor, skip: Tensor, weight: Optional[Tensor],
+                                  bias: Optional[Tensor], slope: Optional[Tensor], mean: Tensor, invstd: Tensor,
+                                  mode: int, kind: int, param: float, T: int, seed: int, offset: int,
+                                  want_dskip: bool = True,
+                                  want_dslope: bool = True) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """(dx, dgamma, dbeta, dskip, dslope) of bn_drop_skip_actx_fwd_raw from x, skip and the key.  dskip = dy * act'(.) is
+    NOT masked; the gradient into the BatchNorm is.  dskip and dslope come back EMPTY as in bn_skip_actx_bwd_raw."""
+    _check_skip_shapes(x, skip, mode)
+    _check_kind(kind, slope)
+    T, seed_c, off_c = _drop_args(T, seed, offset)
+    x, skip, dy = _rows32(x), _rows32(skip), _rows32(dy)
+    N, d = x.shape
+    d_skip = skip.size(1)
+    if dy.shape != (N, d if mode == SKIP_SUM else d_skip + d):
+        raise ValueError(f"bn_drop_skip_actx_bwd_raw: dy {tuple(dy.shape)}, x {tuple(x.shape)}, skip "
+                         f"{tuple(skip.shape)}, mode {mode} do not fit")
+    dx = placement.empty_or_torch((N, d), x.device, reads=(dy, x), streaming=True)
+    dgamma = torch.empty(d, dtype=torch.float32, device=x.device)
+    dbeta = torch.empty_like(dgamma)
+    dslope = torch.empty(1 if (kind == ACT_PRELU and want_dslope) else 0, dtype=torch.float32, device=x.device)
+    if want_dskip and kind != ACT_NONE:
+        dskip = placement.empty_or_torch((N, d_skip), x.device, reads=(dy, skip), streaming=True)
+    else:
+        dskip = torch.empty(0, dtype=torch.float32, device=x.device)
+    w = None if weight is None else weight.detach().contiguous()
+    b = None if bias is None else bias.detach().contiguous()
+    s = _slope32(slope, kind)
+    with torch.cuda.device(x.device):
+        ws, nb = _bn_drop_ws(N, d, x.device)
+        check(lib().mp_bn_train_bwd_drop_skip_act_f32(ptr(dy), dy.stride(0), ptr(x), x.stride(0), ptr(skip),
+                                                      skip.stride(0), N, d, d_skip, mode, ptr(w), ptr(b), ptr(mean),
+                                                      ptr(invstd), kind, float(param), ptr(s), T, seed_c, off_c, ptr(dx),
+                                                      dx.stride(0), ptr(dskip) if dskip.numel() else None,
+                                                      dskip.stride(0) if dskip.numel() else 0, ptr(dgamma), ptr(dbeta),
+                                                      ptr(dslope) if dslope.numel() else None, ptr(ws), nb, _stream()),
+              "mp_bn_train_bwd_drop_skip_act_f32")
+    return dx, dgamma, dbeta, dskip, dslope
+
+
+@_op_bn_drop_skip_actx_bwd_raw.register_fake
+def _(dy, x, skip, weight, bias, slope, mean, invstd, mode, kind, param, T, seed, offset, want_dskip=True,
+      want_dslope=True):
+    dskip = (x.new_empty(skip.shape, dtype=torch.float32) if (want_dskip and kind != ACT_NONE)
+             else x.new_empty((0,), dtype=torch.float32))
+    return (x.new_empty(x.shape, dtype=torch.float32),) + _stats_fake(x)[:2] + (
+        dskip, x.new_empty((1 if (kind == ACT_PRELU and want_dslope) else 0,), dtype=torch.float32))
+
+
+@custom_op("mp::bn_drop_skip_actx", mutates_args=(), device_types="cuda")
+def _op_bn_drop_skip_actx(x: Tensor, skip: Tensor, weight: Optional[Tensor], bias: Optional[Tensor],
+                          slope: Optional[Tensor], eps: float, kind: int, param: float, mode: int, T: int, seed: int,
+                          offset: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """graphgym/models/gnn.py:49-60 behind a last layer [BatchNorm1d, Dropout] in training mode:
+    act(skip + drop(BN(x))) or act(cat(skip, drop(BN(x)))): (out, mean, invstd, var)"""
+    return torch.ops.mp.bn_drop_skip_actx_fwd_raw(x, skip, weight, bias, slope, eps, kind, param, mode, T, seed, offset)
+
+
+@_op_bn_drop_skip_actx.register_fake
+def _(x, skip, weight, bias, slope, eps, kind, param, mode, T, seed, offset):
+    return _skip_fake(x, skip, mode)
+
+
+def _bn_drop_skip_actx_setup(ctx, inputs, output):
+    x, skip, weight, bias, slope, eps, kind, param, mode, T, seed, offset = inputs
+    _, mean, invstd, _ = output
+    ctx.kind, ctx.param, ctx.mode, ctx.d_skip, ctx.drop = kind, param, mode, skip.size(1), (T, seed, offset)
+    ctx.has = (weight is not None, bias is not None, slope is not None)
+    ctx.slope_shape = None if slope is None else slope.shape
+    ctx.save_for_backward(x, skip, weight, bias, slope, mean, invstd)
+
+
+def _bn_drop_skip_actx_backward(ctx, dy, _dmean, _dinvstd, _dvar):
+    x, skip, w, b, s, mean, invstd = ctx.saved_tensors
+    need_x, need_skip, need_w, need_b, need_s = ctx.needs_input_grad[:5]
+    need_s = need_s and ctx.kind == ACT_PRELU
+    dx = dgamma = dbeta = dskip = dslope = None
+    none = ctx.kind == ACT_NONE
+    if need_x or need_w or need_b or need_s or (need_skip and not none):
+        dx, dgamma, dbeta, dskip, dslope = torch.ops.mp.bn_drop_skip_actx_bwd_raw(
+            dy, x, skip, w, b, s, mean, invstd, ctx.mode, ctx.kind, ctx.param, *ctx.drop, need_skip, need_s)
+    if need_skip and none:
+        dskip = dy if ctx.mode == SKIP_SUM else dy[:, :ctx.d_skip]
+    return (dx if need_x else None, dskip if need_skip else None, dgamma if (need_w and ctx.has[0]) else None,
+            dbeta if (need_b and ctx.has[1]) else None, dslope.reshape(ctx.slope_shape) if need_s else None,
+            None, None, None, None, None, None, None)
+
+
+register_autograd("mp::bn_drop_skip_actx", _bn_drop_skip_actx_backward, setup_context=_bn_drop_skip_actx_setup)
+
+
 # ---- softmax cross-entropy over the labelled rows (graphgym/loss.py:53-68, 20-37) -------------------------------
 def _check_ce_shapes(z, y, idx):
     """host-side shape contract (no device read): one label per selected row.  Label VALUES are checked on the device:
@@ -687,22 +1014,90 @@ def _bn_on_engine(bn, x):
             and x.dtype != torch.bfloat16)
 
 
-def bn_act_module(bn, x, act):
-    """``act(bn(x))`` — GraphGym's post-layer (graphgym/models/layer.py:26-35) — for an activation MODULE `act`.  When
-    act_spec knows it and BatchNorm1d.forward's rule holds, this is one engine op (mp::bn_actx): the activation rides the
-    BatchNorm's apply pass, the backward recomputes it from x, and a PReLU slope receives its gradient from the same
-    passes.  Everything else — eval mode, CPU tensors, bf16, a single row, a subclass, per-channel PReLU, a user
-    module — is the torch composition.  `bn`'s running statistics are updated as its own forward would."""
-    spec = act_spec(act)
-    if spec is None or not _bn_on_engine(bn, x):
-        return act(bn(x))
+class Dropout(nn.Dropout):
+    """``nn.Dropout`` over [N, d] node features with the KEYED mask of csrc/draws.h: the mask of a training-mode call is a
+    pure function of ``(seed, step)`` and the element's row and column, the same on the device (mp::dropout_keyed, or
+    fused behind a BatchNorm by bn_act_module / bn_skip_act), on the CPU (dropout_keep_host) and in the backward, which
+    recomputes it: no mask is stored.
+
+    ``seed`` is a Python int, drawn at construction from torch's default CPU generator unless given: torch.manual_seed
+    fixes a model's masks and every layer has its own.  ``step`` is a host counter that advances by one on every
+    training-mode forward; ``set_stream(seed, step)`` sets both.  ``p`` is quantised to T / 65536 (``p_effective``).
+    The numbers are not torch's Philox stream.  ``inplace`` is kept for nn.Dropout's signature (cfg.mem.inplace); a
+    training-mode call always returns a new tensor.  Limits: a captured HIP graph replays the ONE mask of its capture (seed
+    and step are host integers baked into the launch), and a torch.utils.checkpoint recomputation advances the counter,
+    so it draws a different mask than the forward it repeats."""
+
+    def __init__(self, p=0.5, inplace=False, seed=None):
+        super().__init__(p=p, inplace=inplace)
+        self.T = dropout_threshold(p)
+        self.seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
+        self.step = 0
+
+    @property
+    def p_effective(self):
+        return self.T / DROP_ONE
+
+    def set_stream(self, seed, step=0):
+        self.seed, self.step = int(seed), int(step)
+
+    def active(self):
+        """a training-mode call draws a mask (and takes a counter value)"""
+        return self.training and self.T > 0
+
+    def take_step(self):
+        """the counter value of this call; the next call gets the next one"""
+        step = self.step
+        self.step += 1
+        return step
+
+    def forward(self, x):
+        if not self.active():
+            return x
+        step = self.take_step()
+        if x.dim() != 2:
+            raise ValueError("graphgym_amd.nn.Dropout expects [num_nodes, num_features]")
+        if x.is_cuda:
+            out = torch.ops.mp.dropout_keyed(x, self.T, self.seed, step)
+            return out if x.dtype == torch.float32 else out.to(x.dtype)
+        keep = dropout_keep_host(self.seed, step, x.size(0), x.size(1), self.p)
+        return x * keep.to(x.dtype) * dropout_scale(self.p)
+
+    def extra_repr(self):
+        return super().extra_repr() + f", keyed, p_effective={self.p_effective:.6g}"
+
+
+def _drop_fused(drop):
+    """bn_act_module / bn_skip_act's rule for taking `drop` into the BatchNorm pass: the keyed module, drawing a mask"""
+    return isinstance(drop, Dropout) and drop.active()
+
+
+def bn_act_module(bn, x, act, drop=None):
+    """``act(bn(x))`` — GraphGym's post-layer (graphgym/models/layer.py:26-35) — for an activation MODULE `act`, or
+    ``act(drop(bn(x)))`` with a dropout module between them (`act` None: no activation, only with `drop`).  When act_spec
+    knows the activation and BatchNorm1d.forward's rule holds, this is one engine op: mp::bn_actx — the activation rides
+    the BatchNorm's apply pass, the backward recomputes it from x, and a PReLU slope receives its gradient from the same
+    passes — or, with a graphgym_amd.nn.Dropout in training mode, mp::bn_drop_actx, which also draws the keyed mask in
+    those passes and takes the ONE counter value the module's own forward would have taken.  Everything else — eval
+    mode, CPU tensors, bf16, a single row, a subclass, per-channel PReLU, a user module, torch's nn.Dropout — is the
+    torch composition.  `bn`'s running statistics are updated as its own forward would."""
+    spec = (ACT_NONE, None) if act is None else act_spec(act)
+    if spec is None or not _bn_on_engine(bn, x) or (drop is not None and not _drop_fused(drop)) or \
+            (drop is None and act is None):
+        y = bn(x)
+        y = y if drop is None else drop(y)
+        return y if act is None else act(y)
     slope, param = _spec_args(spec)
-    y, mean, _, var_u = torch.ops.mp.bn_actx(x, bn.weight, bn.bias, slope, float(bn.eps), spec[0], param)
+    if drop is None:
+        y, mean, _, var_u = torch.ops.mp.bn_actx(x, bn.weight, bn.bias, slope, float(bn.eps), spec[0], param)
+    else:
+        y, mean, _, var_u = torch.ops.mp.bn_drop_actx(x, bn.weight, bn.bias, slope, float(bn.eps), spec[0], param,
+                                                      drop.T, drop.seed, drop.take_step())
     _update_running_stats(bn, mean, var_u)
     return y
 
 
-def bn_skip_act(bn, x, skip, mode, relu=True, act=None):
+def bn_skip_act(bn, x, skip, mode, relu=True, act=None, drop=None):
     """The tail of GraphGym's skip block (graphgym/models/gnn.py:49-60) around its last layer's BatchNorm:
     ``act(skip + bn(x))`` for mode "skipsum" / SKIP_SUM, ``act(cat((skip, bn(x)), 1))`` for "skipconcat" / SKIP_CONCAT,
     with act = ReLU (``relu=True``), nothing (``relu=False``) or an activation module / callable ``act``.
@@ -712,16 +1107,28 @@ def bn_skip_act(bn, x, skip, mode, relu=True, act=None):
     mp::bn_skip_act for ReLU or no activation (``act=None``), mp::bn_skip_actx for an ``act`` module that act_spec
     knows (statistics, then one pass that normalises, adds or places the skip operand and activates); everything
     else — eval mode with running statistics, CPU tensors, bf16, a single row, an activation without a spec, a
-    BatchNorm that carries its own fused ReLU — is the torch composition, the rule of BatchNorm1d.forward."""
+    BatchNorm that carries its own fused ReLU — is the torch composition, the rule of BatchNorm1d.forward.
+
+    `drop`: the dropout module of the block's last layer, which the reference applies to ``bn(x)`` before the skip
+    operand (graphgym/models/layer.py:26-35 inside gnn.py:49-60): ``act(skip + drop(bn(x)))``.  A graphgym_amd.nn.Dropout
+    in training mode rides the same pass (mp::bn_drop_skip_actx) and takes one counter value, as in bn_act_module; any
+    other dropout module is the composition."""
     mode = _SKIP_MODES[mode]
     _check_skip_shapes(x, skip, mode)
     spec = None if act is None else act_spec(act)
     if not ((act is None or spec is not None) and _bn_on_engine(bn, x) and skip.is_cuda
-            and skip.dtype != torch.bfloat16):
+            and skip.dtype != torch.bfloat16 and (drop is None or _drop_fused(drop))):
         y = bn(x)
+        y = y if drop is None else drop(y)
         z = skip + y if mode == SKIP_SUM else torch.cat((skip, y), 1)
         return act(z) if act is not None else (torch.relu(z) if relu else z)
-    if spec is None:
+    if drop is not None:
+        if spec is None:
+            spec = (ACT_RELU if relu else ACT_NONE, None)
+        slope, param = _spec_args(spec)
+        out, mean, _, var_u = torch.ops.mp.bn_drop_skip_actx(x, skip, bn.weight, bn.bias, slope, float(bn.eps), spec[0],
+                                                             param, mode, drop.T, drop.seed, drop.take_step())
+    elif spec is None:
         out, mean, _, var_u = torch.ops.mp.bn_skip_act(x, skip, bn.weight, bn.bias, float(bn.eps), bool(relu), mode)
     else:
         slope, param = _spec_args(spec)

@@ -391,6 +391,53 @@ int mp_bn_train_bwd_skip_act_f32(const float* dy, int64_t lddy, const float* x, 
                                  float* dgamma, float* dbeta, float* dslope, void* ws, size_t ws_bytes,
                                  mp_stream_t stream);
 
+/* The *_act passes with gnn.dropout between the BatchNorm and the activation (graphgym/models/layer.py:26-35; in a skip
+ * block on the last layer, before the skip operand: gnn.py:49-60), through a KEYED mask m that is never stored:
+ *   q = ceil(d / 4);  key = mix64((mix64(seed + G) ^ offset) + G);  h = mix64((key ^ (r * q + c / 4)) + G)
+ *   m(r, c) = ((h >> 16 * (c % 4)) & 0xffff) >= T          (mix64: the splitmix64 finaliser, G = 0x9E3779B97F4A7C15)
+ * a pure function of seed, offset and the LOGICAL row r and column c of the [N, d] operand x — not of addresses, leading
+ * dimensions or launch geometry.  T = round(p * 65536) in [0, 65536]; kept elements are multiplied by
+ * scale = float(65536 / (65536 - T)) (0 when T = 65536), dropped ones are +0.
+ *   plain : y   = act(m * scale * BN(x))
+ *   SUM   : out = act(skip + m * scale * BN(x))           CONCAT: out = [act(skip) | act(m * scale * BN(x))]
+ *   bwd   : z and m are recomputed; g = dy * act'(z); dskip = g is NOT masked (CONCAT: the left slab never sees the
+ *           mask); the gradient into the BatchNorm is m * scale * g; PRELU's dslope sums dy * min(z, 0) on the masked z.
+ * MP_ACT_NONE has passes of its own here (a layer without activation still drops).  With T = 0 the forward's outputs
+ * are mp_bn_train_fwd_act_f32's / _skip_act_f32's.  Everything else — arguments, dskip / dslope NULL, determinism
+ * (no atomics) — is as in the *_act entries; T outside [0, 65536]: MP_ERR_INVALID_ARG.
+ * The backward keeps what the scale's extra rounding and an fp32 partial sum would lose (the column sums carry their
+ * low-order parts in a second slab per statistics workgroup) and, for ELU / SELU / SILU, takes the derivative at z with
+ * the residue of the fp32 mean folded in (one more read of x); dx = A g + B (x - mean) + C is evaluated in double and
+ * rounded once.  The workspace of the four entries is mp_bn_drop_ws_bytes': mp_bn_act_ws_bytes' layout with two partial
+ * slabs per statistics workgroup, then three double vectors of d. */
+int mp_bn_drop_ws_bytes(int64_t N, int32_t d, size_t* bytes_host);
+int mp_bn_train_fwd_drop_act_f32(const float* x, int64_t ldx, int64_t N, int32_t d, const float* gamma,
+                                 const float* beta, float eps, int act, float act_param, const float* slope, int32_t T,
+                                 uint64_t seed, uint64_t offset, float* y, int64_t ldy, float* mean, float* invstd,
+                                 float* var_unbiased, void* ws, size_t ws_bytes, mp_stream_t stream);
+int mp_bn_train_bwd_drop_act_f32(const float* dy, int64_t lddy, const float* x, int64_t ldx, int64_t N, int32_t d,
+                                 const float* gamma, const float* beta, const float* mean, const float* invstd,
+                                 int act, float act_param, const float* slope, int32_t T, uint64_t seed,
+                                 uint64_t offset, float* dx, int64_t lddx, float* dgamma, float* dbeta, float* dslope,
+                                 void* ws, size_t ws_bytes, mp_stream_t stream);
+int mp_bn_train_fwd_drop_skip_act_f32(const float* x, int64_t ldx, const float* skip, int64_t ldskip, int64_t N,
+                                      int32_t d, int32_t d_skip, int mode, const float* gamma, const float* beta,
+                                      float eps, int act, float act_param, const float* slope, int32_t T,
+                                      uint64_t seed, uint64_t offset, float* out, int64_t ldo, float* mean,
+                                      float* invstd, float* var_unbiased, void* ws, size_t ws_bytes,
+                                      mp_stream_t stream);
+int mp_bn_train_bwd_drop_skip_act_f32(const float* dy, int64_t lddy, const float* x, int64_t ldx, const float* skip,
+                                      int64_t ldskip, int64_t N, int32_t d, int32_t d_skip, int mode,
+                                      const float* gamma, const float* beta, const float* mean, const float* invstd,
+                                      int act, float act_param, const float* slope, int32_t T, uint64_t seed,
+                                      uint64_t offset, float* dx, int64_t lddx, float* dskip, int64_t lddskip,
+                                      float* dgamma, float* dbeta, float* dslope, void* ws, size_t ws_bytes,
+                                      mp_stream_t stream);
+/* The mask alone over an [N, d] fp32 view: out = m * scale * x (a dropout with no BatchNorm in front of it).  Its
+ * backward is the same call on dy. */
+int mp_dropout_keyed_f32(const float* x, int64_t ldx, int64_t N, int32_t d, int32_t T, uint64_t seed, uint64_t offset,
+                         float* out, int64_t ldo, mp_stream_t stream);
+
 /* ------------------------------------------------------------------ *
  * Aggregate -> transform in one kernel                                *
  * ------------------------------------------------------------------ */
