@@ -511,7 +511,8 @@ int mp_id_fixup_f32(const int32_t* rows, const int32_t* crp, const int32_t* slot
  *   (rows / crp / slot / val_id: as for mp_id_fixup_f32; id_rows [N] uint8 = 1 exactly on `rows`).
  * Every row of Q is written exactly once; the identity entries (1 % of the operator at 1 % identity nodes) are gathered
  * from an [n_id, F] matrix.  n_rows = 0: Q = 0.  F = 128, 256 or 512, 16-byte aligned rows; MP_ERR_UNSUPPORTED otherwise.
- * mp_id_rows_f32 is the small kernel alone (the row's old contents are not read). */
+ * mp_id_rows_f32 is the small kernel alone (the row's old contents are not read): it writes out[rows[k], :] for the
+ * n_rows listed rows; every other row of out is left untouched and is undefined in a fresh buffer. */
 int mp_idgnn_agg_tiles_f32(const int32_t* rowptr, const int32_t* col, const float* val, int64_t N, const float* X,
                            int64_t ldx, int32_t F, const uint8_t* id_rows, const int32_t* rows, const int32_t* crp,
                            const int32_t* slot, const float* val_id, int64_t n_rows, const float* Z, int64_t ldz, float* P,
