@@ -12,6 +12,8 @@ def _defaults():
     cfg = types.SimpleNamespace()
     cfg.device = "auto"                      # config.py:33
     cfg.num_threads = 6                      # config.py:57
+    cfg.round = 4                            # config.py:60 (metrics.py: the digits an epoch's statistics are rounded to)
+    cfg.metric_best = "auto"                 # config.py:45
     cfg.dataset = types.SimpleNamespace(transform="none", augment_feature=[], task="node",
                                         edge_dim=128,                    # config.py:145
                                         edge_train_mode="all", edge_message_ratio=0.8,
@@ -20,7 +22,8 @@ def _defaults():
                                         node_encoder=False, node_encoder_name="Atom", node_encoder_bn=True,
                                         edge_encoder=False, edge_encoder_name="Bond", edge_encoder_bn=True,
                                         encoder_dim=128)                 # config.py:121-142 (encoders.py)
-    cfg.model = types.SimpleNamespace(graph_pooling="add", loss_fun="cross_entropy")      # config.py:285-301
+    cfg.model = types.SimpleNamespace(graph_pooling="add", loss_fun="cross_entropy",      # config.py:285-301
+                                      size_average="mean", thresh=0.5)                    # config.py:284,287 (metrics.py)
     # config.py:212-248 (samplers.py); train.train_parts (read by loader_pyg.py:218) has no default there or here
     cfg.train = types.SimpleNamespace(batch_size=16, sampler="full_batch", iter_per_epoch=32, walk_length=4,
                                       neighbor_sizes=[20, 15, 10, 5])

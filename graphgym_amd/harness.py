@@ -11,6 +11,8 @@ model shapes of the reference's two entry points and its training step order.
                    (node head + label gather head.py:19-37, or graph head with ego add-pool head.py:96-119)
     train_step     zero_grad -> forward -> loss -> backward -> [gradient all-reduce] -> step
                    (graphgym/train.py:18-25, 47-56)
+    eval_epoch     model.eval() -> forward -> loss and statistics into a metrics.Meter, nothing read on the host
+                   (graphgym/train.py:67-80)
     tfg_loss       mean softmax-CE over node_label_index + 5e-4 * sum ||kernel||^2 / 2
                    (graphgym/loss.py:53-68)
 """
@@ -510,6 +512,18 @@ def train_step(model, optimizer, forward_loss, bucket=None):
         bucket.all_reduce_mean()
     optimizer.step()
     return loss.detach()
+
+
+@torch.no_grad()
+def eval_epoch(model, loader, meter):
+    """train.py:67-80 on a graphgym_amd.metrics.Meter: the model's raw outputs go into meter.update_logits, which
+    accumulates the statistics and the loss on the device — no copy of `true` / `pred_score` to the host and no
+    loss.item() per batch.  The epoch's numbers are meter.compute() (one device-to-host copy)."""
+    model.eval()
+    for batch in loader:
+        pred, true = model(batch)
+        meter.update_logits(pred, true)
+    return meter
 
 
 class GraphedTrainStep:
