@@ -49,10 +49,11 @@ __device__ __forceinline__ float act_bwd(float dy, float z, float p) {
 __device__ __forceinline__ float act_dslope(float z) { return z > 0.f ? 0.f : z; }
 
 // runtime kind -> template argument: f receives std::integral_constant<int, MP_ACT_*>; false for a kind that is not
-// one of the six activations (MP_ACT_NONE has no kernel of its own: its callers go to the plain passes)
+// MP_ACT_NONE or one of the six activations
 template <class Fn>
 static inline bool with_act(int act, Fn&& f) {
   switch (act) {
+    case MP_ACT_NONE: f(std::integral_constant<int, MP_ACT_NONE>{}); return true;
     case MP_ACT_RELU: f(std::integral_constant<int, MP_ACT_RELU>{}); return true;
     case MP_ACT_LRELU: f(std::integral_constant<int, MP_ACT_LRELU>{}); return true;
     case MP_ACT_PRELU: f(std::integral_constant<int, MP_ACT_PRELU>{}); return true;

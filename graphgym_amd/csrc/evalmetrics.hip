@@ -5,7 +5,7 @@
 //   counters  int64, one integer atomic per workgroup and counter: order-independent
 //   sums      double, per-thread over a fixed assignment of elements -> per-workgroup partial in thread order ->
 //             one workgroup adds the partials in a fixed order and ONE thread adds the result to the state word
-//             (the bn_block_sum / bn_col_sums pattern of bn_shared.h; no float atomics)
+//             (the bn_block_sum / bn_col_sums pattern of bn_kernels.h; no float atomics)
 // Every index is 64-bit, and no label, index or class id reaches an address before it has been range-checked.
 #include "common.h"
 #include "../../include/mp_eval.h"
