@@ -540,11 +540,11 @@ int mp_sddmm_dot_stream_f32(const int32_t* row_of, const int32_t* col, int64_t n
 int mp_spmm_heads_max_da_f32(const int32_t* row_of, const int32_t* col, int64_t nnz, const int32_t* argmax,
                              int64_t ldm, const float* dY, int64_t ldy, const float* V, int64_t ldv, int32_t d,
                              int32_t heads, float* da, mp_stream_t stream) {
-  if (!row_of || !col || !argmax || !dY || !V || !da || nnz < 0 || d <= 0 || heads < 1 || d % heads)
-    return MP_ERR_INVALID_ARG;
+  if (nnz < 0 || d <= 0 || heads < 1 || d % heads) return MP_ERR_INVALID_ARG;
   if (ldm < d || ldy < d || ldv < d) return MP_ERR_INVALID_ARG;
   if (nnz >= INT32_MAX) return MP_ERR_UNSUPPORTED;
-  if (nnz == 0) return MP_OK;
+  if (nnz == 0) return MP_OK;         // no entry: the per-entry arrays (and those of an operator without rows) may be NULL
+  if (!row_of || !col || !argmax || !dY || !V || !da) return MP_ERR_INVALID_ARG;
   return sddmm_stream_launch<true>(row_of, col, nnz, dY, ldy, V, ldv, d, heads, 1.0f, da, argmax, ldm,
                                    as_stream(stream));
 }

@@ -966,8 +966,9 @@ extern "C" {
 int mp_dense_fused_f32(const float* P, int64_t ldp, const float* W, const float* Q, int64_t ldq,
                        const float* Wid, const float* bias, int act, float* out, int64_t ldo, int64_t M,
                        int32_t F, int32_t d, mp_stream_t stream) {
-  if (M < 0 || F <= 0 || d <= 0 || !P || !W || !out || ldp < F || ldo < d) return MP_ERR_INVALID_ARG;
-  if ((Q == nullptr) != (Wid == nullptr) || (Q && ldq < F)) return MP_ERR_INVALID_ARG;
+  if (M < 0 || F <= 0 || d <= 0 || !W || (M > 0 && (!P || !out)) || ldp < F || ldo < d) return MP_ERR_INVALID_ARG;
+  if (M > 0 && (Q == nullptr) != (Wid == nullptr)) return MP_ERR_INVALID_ARG;   // (Q of no rows has no address)
+  if (Q && ldq < F) return MP_ERR_INVALID_ARG;
   if (act != MP_ACT_NONE && act != MP_ACT_RELU) return MP_ERR_INVALID_ARG;
   if (M == 0) return MP_OK;
   // 16-byte vector loads need operand widths in multiples of 8 (F) / 4 (d) and aligned rows; else scalar loaders
@@ -1086,7 +1087,7 @@ int mp_dense_wgrad_f32(const float* P, int64_t ldp, const float* G, int64_t ldg,
 int mp_dense_wgrad_relu_f32(const float* P, int64_t ldp, const float* G, int64_t ldg, const float* Y, int64_t ldy,
                             float* GM, int64_t ldgm, int64_t M, int32_t F, int32_t d, float* dW, float* dbias,
                             void* ws, size_t ws_bytes, mp_stream_t stream) {
-  if (!Y) return MP_ERR_INVALID_ARG;
+  if (M != 0 && !Y) return MP_ERR_INVALID_ARG;
   return wgrad_common(P, ldp, G, ldg, Y, ldy, GM, ldgm, M, F, d, dW, dbias, ws, ws_bytes, as_stream(stream));
 }
 

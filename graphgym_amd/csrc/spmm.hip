@@ -829,14 +829,15 @@ static int agg_common(const int32_t* rowptr, const int32_t* col, const float* va
                       int32_t* argmax, void* ws, size_t ws_bytes, hipStream_t st,
                       const float* col_scale = nullptr, int l2norm = 0, float l2_eps = 1e-12f, int heads = 1,
                       const EdgeOperands* eo = nullptr) {
-  if (!rowptr || !plan || !counts || !X || !Y) return MP_ERR_INVALID_ARG;
+  if (!rowptr || !plan || !counts) return MP_ERR_INVALID_ARG;
   if (N < 0 || d <= 0 || ldx < d || ldy < d) return MP_ERR_INVALID_ARG;
   if (reduce < MP_SUM || reduce > MP_MAX) return MP_ERR_INVALID_ARG;
   if (act != MP_ACT_NONE && act != MP_ACT_RELU) return MP_ERR_INVALID_ARG;
   if (Q && ldq < d) return MP_ERR_INVALID_ARG;
   if (S && lds < d) return MP_ERR_INVALID_ARG;
   if (N >= INT32_MAX) return MP_ERR_UNSUPPORTED;
-  if (N == 0) return MP_OK;
+  if (N == 0) return MP_OK;           // no row: the arrays of N rows (Y; X of a square operator) may have no address
+  if (!X || !Y) return MP_ERR_INVALID_ARG;
   const int32_t n_seg = counts[0], n_piece = counts[2];
   if (n_seg < 1) return MP_ERR_INVALID_ARG;
   if (!col && n_piece > 0) return MP_ERR_INVALID_ARG;
@@ -991,7 +992,7 @@ int mp_idgnn_agg_f32(const int32_t* rowptr, const int32_t* col_marked, const flo
                      const int32_t* plan, const int32_t* counts_host, const float* X, int64_t ldx,
                      float* P, int64_t ldp, float* Q, int64_t ldq, int32_t d, void* ws,
                      size_t ws_bytes, mp_stream_t stream) {
-  if (!Q) return MP_ERR_INVALID_ARG;
+  if (N != 0 && !Q) return MP_ERR_INVALID_ARG;
   return agg_common<F32>(rowptr, col_marked, val, N, plan, counts_host, X, ldx, P, ldp, Q, ldq, d, MP_SUM,
                          nullptr, 0, 0.f, nullptr, MP_ACT_NONE, nullptr, ws, ws_bytes, as_stream(stream));
 }
@@ -1048,11 +1049,12 @@ int mp_spmm_csr_edge_heads_f32(const int32_t* rowptr, const int32_t* col, const 
 static int edge_bwd_launch(const int32_t* rowptr, const int32_t* eid, const float* val, int32_t heads,
                            const int32_t* argmax, int64_t N, int64_t nnz, int reduce, const float* dY, int64_t ldy,
                            int32_t d, float* dM, int64_t ldm, hipStream_t st) {
-  if (!rowptr || !eid || !dY || !dM || N < 0 || nnz < 0 || d < 1) return MP_ERR_INVALID_ARG;
-  if (reduce < MP_SUM || reduce > MP_MAX || (reduce == MP_MAX && !argmax)) return MP_ERR_INVALID_ARG;
+  if (!rowptr || N < 0 || nnz < 0 || d < 1) return MP_ERR_INVALID_ARG;
+  if (reduce < MP_SUM || reduce > MP_MAX) return MP_ERR_INVALID_ARG;
   if (ldy < d || ldm < d) return MP_ERR_INVALID_ARG;
   if (N >= INT32_MAX || nnz >= INT32_MAX) return MP_ERR_UNSUPPORTED;
-  if (N == 0 || nnz == 0) return MP_OK;
+  if (N == 0 || nnz == 0) return MP_OK;     // no row or no entry: eid, and dY / argmax of no rows, may have no address
+  if (!eid || !dY || !dM || (reduce == MP_MAX && !argmax)) return MP_ERR_INVALID_ARG;
   const int32_t hw = heads > 1 ? d / heads : d;
   if (reduce == MP_MAX) {
     const dim3 grid(row_grid(N));
@@ -1113,7 +1115,7 @@ int mp_idgnn_agg_bf16(const int32_t* rowptr, const int32_t* col_marked, const fl
                       const int32_t* plan, const int32_t* counts_host, const void* X, int64_t ldx,
                       void* P, int64_t ldp, void* Q, int64_t ldq, int32_t d, void* ws,
                       size_t ws_bytes, mp_stream_t stream) {
-  if (!Q) return MP_ERR_INVALID_ARG;
+  if (N != 0 && !Q) return MP_ERR_INVALID_ARG;
   return agg_common<Bf16>(rowptr, col_marked, val, N, plan, counts_host, (const uint16_t*)X, ldx, (uint16_t*)P, ldp,
                           (uint16_t*)Q, ldq, d, MP_SUM, nullptr, 0, 0.f, nullptr, MP_ACT_NONE, nullptr, ws, ws_bytes,
                           as_stream(stream));

@@ -224,7 +224,7 @@ class CSRGraph:
         g = self.__dict__.get("_edge_op")
         if g is None:
             cols = torch.arange(self.nnz, dtype=torch.int32, device=self.device)
-            g = CSRGraph(self.rowptr, cols, self.val, None, self.num_nodes, self.nnz, max(self.nnz, 1))
+            g = CSRGraph(self.rowptr, cols, self.val, None, self.num_nodes, self.nnz, self.nnz)
             self.__dict__["_edge_op"] = g
         return g
 
@@ -236,7 +236,7 @@ class CSRGraph:
         cache = self.__dict__.setdefault("_input_edge_op", {})
         g = cache.get(int(n_edges))
         if g is None:
-            g = CSRGraph(self.rowptr, self.eid, self.val, None, self.num_nodes, self.nnz, max(int(n_edges), 1))
+            g = CSRGraph(self.rowptr, self.eid, self.val, None, self.num_nodes, self.nnz, int(n_edges))
             g._plan = self.plan()              # same rowptr, same segmentation
             cache[int(n_edges)] = g
         return g
@@ -352,7 +352,7 @@ class CSRGraph:
                 run = os.environ.get("MP_SYM_CHECK", "0") == "1"
             if not run:
                 return False                      # (not cached: a later explicit check may still run)
-            if self.num_nodes == self.num_cols and self.nnz > 0:
+            if self.num_nodes == self.num_cols:            # (an operator without entries equals its transpose)
                 L = lib()
                 _built("is_symmetric")
                 flag = torch.empty(1, dtype=torch.int32, device=self.device)

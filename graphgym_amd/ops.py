@@ -54,6 +54,10 @@ def _raw_spmm(g, x, reduce, S=None, self_scale=0.0, bias=None, relu=False, want_
     mp_spmm_csr_f32 on x.float() with the same plan, rounded once to bf16.  The tile kernels have no bf16 form."""
     L = lib()
     N, d = g.num_nodes, x.size(1)
+    if x.size(0) == 0 and N > 0 and g.nnz == 0:
+        # an operator without columns (and so without entries): nothing reads X, the entry point — which cannot see the
+        # column count — wants an address; the rows still get their self term, bias and activation
+        x = x.new_zeros((1, d))
     y = out if out is not None else placement.empty_or_torch((N, d), x.device, reads=(x,), dtype=x.dtype)
     if (x.dtype == torch.float32 and reduce in (_lib.SUM, _lib.MEAN, _lib.MAX) and d in AGG_TILES_WIDTHS
             and N >= AGG_TILES_MIN_ROWS and bias is None
@@ -529,6 +533,18 @@ def gather_rows(x, ids):
 
 # ---- attention pieces --------------------------------------------------------
 
+def _agg_of_nothing(N, d, x, bias=None, want_argmax=False, out=None):
+    """(y, argmax or None) of an aggregation over an operator without entries, whose per-entry arrays have no address to
+    hand to a kernel (the zero-extent rule): every row is empty, so y = 0 + bias — a destination's own
+    term t rides in the entries and goes with them — and argmax = -1"""
+    y = out if out is not None else torch.empty((N, d), dtype=x.dtype, device=x.device)
+    if bias is None:
+        y.zero_()
+    else:
+        y.copy_(bias.detach().to(y.dtype).expand(N, d))
+    return y, (torch.full((N, d), -1, dtype=torch.int32, device=x.device) if want_argmax else None)
+
+
 def _raw_sddmm_dot(g, A, B, heads, scale, idx=None):
     """s[e, h] = scale * <A[row_e, slice h], B[idx[e], slice h]>; idx [nnz] int32: the row of B an entry reads (default:
     its column, g.col)"""
@@ -570,6 +586,8 @@ def _raw_heads_agg(g, w, x, heads, reduce=_lib.SUM, want_argmax=False, edge=None
         eid = _eid_checked(g, m.size(0))
         if m.size(0) == 0:      # every entry is an inserted loop: the kernel still reads (and drops) row 0
             m = torch.zeros((1, d), dtype=torch.float32, device=x.device)
+    if g.nnz == 0:              # no entry: col, eid and w have no address; every row is empty
+        return _agg_of_nothing(N, d, x, bias, want_argmax)
 
     def one_head(vals, cs=slice(None), out=None):
         gh = g.with_values(vals.contiguous())
@@ -767,9 +785,10 @@ class _EdgeSoftmax(torch.autograd.Function):
         s = s.contiguous()
         heads = s.size(1)
         p = torch.empty_like(s)
-        with torch.cuda.device(s.device):
-            check(L.mp_csr_row_softmax_f32(ptr(g.rowptr), g.num_nodes, heads, ptr(s), ptr(p), _stream()),
-                  "mp_csr_row_softmax_f32")
+        if g.nnz:               # (the entry point cannot see nnz: without entries s and p have no address)
+            with torch.cuda.device(s.device):
+                check(L.mp_csr_row_softmax_f32(ptr(g.rowptr), g.num_nodes, heads, ptr(s), ptr(p), _stream()),
+                      "mp_csr_row_softmax_f32")
         ctx.g = g
         ctx.save_for_backward(p)
         return p
@@ -835,10 +854,11 @@ class _SpmmEdgeValues(torch.autograd.Function):
                 da = _raw_heads_max_da(g, argmax, dy, V, heads)
             if need_v:
                 dV = torch.zeros_like(V)
-                with torch.cuda.device(V.device):
-                    check(lib().mp_spmm_heads_max_bwd_f32(ptr(g.col), ptr(a), heads, ptr(argmax), g.num_nodes, V.size(1),
-                                                          ptr(dy), dy.stride(0), ptr(dV), dV.stride(0), _stream()),
-                          "mp_spmm_heads_max_bwd_f32")
+                if g.nnz:
+                    with torch.cuda.device(V.device):
+                        check(lib().mp_spmm_heads_max_bwd_f32(ptr(g.col), ptr(a), heads, ptr(argmax), g.num_nodes,
+                                                              V.size(1), ptr(dy), dy.stride(0), ptr(dV), dV.stride(0),
+                                                              _stream()), "mp_spmm_heads_max_bwd_f32")
             return da, dV, None, None, None
         if ctx.reduce == _lib.MEAN:
             dy = (dy / g.entry_counts().clamp(min=1.0)[:, None]).contiguous()
@@ -937,6 +957,8 @@ def _op_spmm_max_bwd_raw(dy: Tensor, argmax: Tensor, graph: int) -> Tensor:
     dy = dy.contiguous()
     N, d = dy.shape
     dx = torch.zeros((g.num_cols, d), dtype=torch.float32, device=dy.device)
+    if g.nnz == 0:              # no entry won anything (the entry point cannot see nnz: col has no address)
+        return dx.to(dy.dtype)
     # a bf16 gradient is accumulated in fp32 and rounded once
     name = "mp_spmm_max_bwd_bf16" if dy.dtype == torch.bfloat16 else "mp_spmm_max_bwd_f32"
     with torch.cuda.device(dy.device):
@@ -1364,6 +1386,9 @@ def agg_dense(g, x, W, bias=None, relu=False, self_scale=0.0, reduce="sum"):
     _require_hip(x, "x")
     if g.num_cols != g.num_nodes and self_scale != 0.0:
         raise ValueError("the self term needs a square operator")
+    if _lib.REDUCE[reduce] == _lib.MAX:
+        # the backward runs on the transposed (mean) operator: a max has no such form, and no layer asks for it
+        raise ValueError("agg_dense takes reduce 'sum' / 'add' or 'mean', not 'max' (spmm + dense_fused has the max)")
     want_P = torch.is_grad_enabled() and W.requires_grad     # inference: no aggregated rows written
     return torch.ops.mp.agg_dense(x, W, bias, g.handle, _lib.REDUCE[reduce], float(self_scale), bool(relu), want_P)[0]
 
@@ -1476,6 +1501,8 @@ def _raw_spmm_edge(g, x, m, t=None, bias=None, reduce=_lib.SUM, want_argmax=Fals
     N, d = g.num_nodes, x.size(1)
     if eid is None:
         eid = _eid_checked(g, m.size(0))
+    if g.nnz == 0:          # no entry: col and eid have no address; every row is empty
+        return _agg_of_nothing(N, d, x, bias, want_argmax, out)
     if m.size(0) == 0:      # every entry is an inserted loop: the kernel still reads (and drops) row 0
         m = torch.zeros((1, d), dtype=torch.float32, device=x.device)
     y = out if out is not None else placement.empty_or_torch((N, d), x.device, reads=(x, m))
@@ -1511,6 +1538,8 @@ def _op_spmm_edge_bwd_raw(dy: Tensor, argmax: Tensor, graph: int, reduce: int, n
     dy = dy if dy.stride(-1) == 1 else dy.contiguous()
     N, d = dy.shape
     dm = torch.zeros((n_edges, d), dtype=torch.float32, device=dy.device)
+    if n_edges == 0:            # (the entry point cannot see n_edges: every entry is an inserted loop, dm has no address)
+        return dm
     with torch.cuda.device(dy.device):
         check(lib().mp_spmm_edge_bwd_f32(ptr(g.rowptr), ptr(g.eid), ptr(g.val), ptr(_none_if_empty(argmax)), N, g.nnz,
                                          reduce, ptr(dy), dy.stride(0), d, ptr(dm), dm.stride(0), _stream()),
@@ -1528,6 +1557,8 @@ def _op_spmm_edge_dt_raw(dy: Tensor, argmax: Tensor, graph: int, reduce: int) ->
     """dt [N, d] of spmm_edge, elementwise: t[r] rides in every entry of row r — (the sum of the row's values [over its
     entry count for mean]) * dy; max: each column's winner carries it once — val[argmax] * dy, 0 for an empty row"""
     g = from_handle(graph)
+    if g.nnz == 0:              # no entry carries t
+        return torch.zeros_like(dy)
     if reduce == _lib.MAX:
         dt = dy if g.val is None else g.val[argmax.clamp(min=0).long()] * dy
         return torch.where(argmax >= 0, dt, torch.zeros_like(dt))
@@ -1763,7 +1794,9 @@ def _op_spmm_edge_heads_bwd_raw(dy: Tensor, w: Tensor, x: Tensor, m: Tensor, t: 
                                                    N, g.nnz, reduce, ptr(dy0), dy0.stride(0), d, ptr(dm), dm.stride(0),
                                                    _stream()), "mp_spmm_edge_heads_bwd_f32")
     if want & _EH_T and t is not None:
-        if is_max:     # each column's winner carries t once
+        if g.nnz == 0:  # no entry carries t
+            dt = torch.zeros_like(dy)
+        elif is_max:   # each column's winner carries t once
             am = argmax.long()
             head_of = torch.arange(d, device=dy.device) // hw
             dt = w.reshape(-1)[(am.clamp(min=0) * heads + head_of)] * dy
@@ -1966,6 +1999,8 @@ def _op_embed_sum_bwd_raw(dy: Tensor, codes: Tensor, offsets: List[int], n_codes
     disjoint: the caller's promise that the K codes of a row lie in K separate tables (embed_sum: codes checked against
     tables at strictly increasing offsets), which lets K = 3 / 9 update all K accumulators of a row at once"""
     dy = dy if dy.dim() == 2 and dy.stride(1) == 1 else dy.contiguous()
+    if dy.size(0) == 0:         # no item: nothing reaches the table
+        return torch.zeros((n_codes, dy.size(1)), dtype=torch.float32, device=dy.device)
     if code_reduce_path(n_codes) == "operator":
         return _code_reduce_fallback(dy, codes, offsets, n_codes)
     return _raw_code_reduce(dy, codes, n_codes, K=codes.size(1), off=_offsets_dev(offsets, dy.device),
@@ -2057,6 +2092,8 @@ def _op_spmm_code_bwd_raw(dy: Tensor, argmax: Tensor, qe: Tensor, graph: int, re
     (/ the row's entry count), max over each column's winning entry"""
     g = from_handle(graph)
     dy = dy if dy.dim() == 2 and dy.stride(1) == 1 else dy.contiguous()
+    if g.nnz == 0:              # no entry: nothing reaches the table
+        return torch.zeros((n_codes, dy.size(1)), dtype=torch.float32, device=dy.device)
     if reduce == _lib.MAX:
         return _raw_code_reduce(dy, qe, n_codes, w=g.val, sel=argmax)[0]
     w = g.val

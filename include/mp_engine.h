@@ -37,6 +37,11 @@ extern "C" {
 
 typedef void* mp_stream_t; /* hipStream_t */
 
+/* Zero extents: an array whose extent is an ARGUMENT of the call (nnz, n, M, n_rows; N for arrays of N rows) may be NULL
+ * when that extent is 0 — the call then returns MP_OK without a launch — and is MP_ERR_INVALID_ARG when NULL at a
+ * non-zero extent.  Required arrays whose extent the call cannot see (col / eid / the head weights of the aggregation
+ * entries, which get N but not nnz; X, which has one row per COLUMN) must have an address: a caller with an empty one
+ * does not call, or hands in a row nothing reads (the zero-extent rule). */
 enum mp_status {
   MP_OK = 0,
   MP_ERR_INVALID_ARG = 1, /* null pointer, negative size, bad enum */
