@@ -5,7 +5,7 @@ import ctypes as C
 import torch
 
 from ._lib import ALLOC_FN, FREE_FN, EgoResult, EngineError, check, lib, ptr
-from .graph import CSRGraph, _require_hip, _stream  # noqa: F401
+from .graph import CSRGraph, _require_hip, _stream, tensor_stamp  # noqa: F401
 
 TAG_SCRATCH, TAG_EDGES, TAG_ORIG, TAG_EGO_OF, TAG_ROWPTR, TAG_COL, TAG_EID = range(7)
 FLAG_CSR, FLAG_CSR_SELF_LOOPS = 1, 2
@@ -100,5 +100,5 @@ def ego_batch(base, centres, radius, csr=None):
         g = CSRGraph(outs[TAG_ROWPTR].view(torch.int32)[:n_out + 1], outs[TAG_COL].view(torch.int32)[:nnz], None,
                      outs[TAG_EID].view(torch.int32)[:nnz], n_out, nnz)
         g.symmetric = True
-        g._ego_ids = ((ids.data_ptr(), ids.numel(), ids._version), ids)      # id_branch(ids) takes the ego-batch shortcut
+        g._ego_ids = (tensor_stamp(ids), ids)      # id_branch(ids) takes the ego-batch shortcut
     return ei, orig, ids, ego_of, g

@@ -15,6 +15,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .graph import tensor_stamp
 
 # The feature dims of ogb.utils.features.get_atom_feature_dims() / get_bond_feature_dims(), used when ogb is not
 # importable.  These are the values of ogb 1.x as recalled from the library; no copy of ogb was at hand to confirm
@@ -45,7 +46,7 @@ def cached_codes(holder, field, codes, dims, make=None):
     batch) per (field, tensor, dims) like the graph cache: one range check per batch, not one per call.  make: a map
     from the checked [R, K] codes to what is stored (ogbconv: the combined bond code)."""
     key = (field, tuple(int(d) for d in dims), make)
-    stamp = (codes.data_ptr(), tuple(codes.shape), codes._version)
+    stamp = tensor_stamp(codes)
     cache = None
     if holder is not None:
         cache = getattr(holder, "_mp_code_cache", None)

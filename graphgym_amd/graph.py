@@ -79,6 +79,27 @@ def tag_hot_columns(col, hot):
     return col | tag.index_select(0, col)
 
 
+def tensor_stamp(t):
+    """The key under which a cache remembers the tensor a structure was built for: (device, dtype, data_ptr, shape,
+    strides, _version).  Two tensors with equal stamps read the same elements of the same memory as the same type, in
+    the same order — a tensor re-sliced into a new Python object with the same geometry (`ids[:k]` taken afresh every
+    step) hits, while a prefix against a strided view, `pairs.t()` against `pairs.view(2, E)`, or an int64 tensor against
+    an int32 view of its memory do not collide (address, element count and version alone are equal for each of these).
+    Every cache keyed on a caller's tensor uses it: CSRGraph.select_rows / mark_ids / id_branch and the ego shortcut
+    (ego.ego_batch), layers.get_graph / seed_graph_cache, encoders.cached_codes, and the one-hot operators of ops
+    (_code_reduce_fallback, _entry_reduce_fallback).
+
+    Contract:
+      * an in-place torch op on the tensor (copy_, index assignment, add_, an out= argument) bumps `_version`: seen,
+        the structure is rebuilt;
+      * a rewrite through `.data`, or through a raw pointer (a kernel handed `data_ptr()`), is NOT seen: `.data`
+        shares the memory under a version counter of its own.  Nothing in the engine refills a tensor it has handed
+        out that way; a caller who does must hand a new tensor;
+      * the caller otherwise hands a new tensor for new contents.  A cache holds the tensor it keyed on for as long as
+        the entry lives, so the address of a live entry cannot be given to another allocation."""
+    return (t.device, t.dtype, t.data_ptr(), tuple(t.shape), tuple(t.stride()), t._version)
+
+
 _HANDLES = weakref.WeakValueDictionary()     # int handle -> CSRGraph: how a graph crosses the torch.ops.mp.* boundary
 _next_handle = itertools.count(1)
 
@@ -195,7 +216,7 @@ class CSRGraph:
     def select_rows(self, rows):
         """the rows `rows` (LongTensor, any order) as a rectangular operator [len(rows), num_cols];
         cached per index tensor (a batch's node_id_index is the same tensor every step)"""
-        stamp = (rows.data_ptr(), rows.numel(), rows._version)
+        stamp = tensor_stamp(rows)
         cache = self.__dict__.setdefault("_row_subsets", {})
         if stamp not in cache:
             if len(cache) > 8:
@@ -517,7 +538,7 @@ class CSRGraph:
         (the mark depends only on the pattern, so graphs sharing a pattern share it)"""
         _require_hip(id_index, "id_index")
         owner = getattr(self, "_pattern_of", None) or self
-        stamp = (id_index.data_ptr(), id_index.numel(), id_index._version)
+        stamp = tensor_stamp(id_index)
         cache = owner.__dict__.setdefault("_id_marks", {})
         if stamp not in cache:
             if len(cache) > 8:
@@ -534,7 +555,7 @@ class CSRGraph:
         slot [n_e] int32 (position of the entry's source in id_index), val [n_e] fp32 or None, defer [N] uint8
         (1 on `rows`), and t: A_id^T as a CSRGraph [n_id x N] (for the backward pass)."""
         _require_hip(id_index, "id_index")
-        stamp = (id_index.data_ptr(), id_index.numel(), id_index._version)
+        stamp = tensor_stamp(id_index)
         cache = self.__dict__.setdefault("_id_branch", {})
         if stamp not in cache:
             if len(cache) > 8:

@@ -25,7 +25,7 @@ from torch.nn import Parameter
 
 from . import ops
 from .config import cfg
-from .graph import CSRGraph
+from .graph import CSRGraph, tensor_stamp
 
 
 # ---- parameter init: torch_geometric.nn.inits.glorot / zeros [3P]; keras glorot_uniform ----
@@ -58,7 +58,7 @@ def get_graph(holder, edge_index, num_nodes, *, dst_row=1, loops="none", norm=No
     key = (dst_row, loops, norm, float(fill))
     cache = None
     if holder is not None and edge_weight is None:
-        stamp = (edge_index.data_ptr(), tuple(edge_index.shape), edge_index._version, int(num_nodes))
+        stamp = (tensor_stamp(edge_index), int(num_nodes))
         cache = getattr(holder, "_mp_graph_cache", None)
         if cache is None or cache.get("stamp") != stamp:
             cache = {"stamp": stamp, "edge_index": edge_index}     # holding the tensor keeps its address unique
@@ -93,7 +93,7 @@ def seed_graph_cache(holder, edge_index, num_nodes, g, loops):
     keys hold a graph of the same operator (shared plan and caches) whose eid is remapped on its first read."""
     if not g.symmetric:
         raise ValueError("seed_graph_cache needs a graph flagged symmetric (ego.ego_batch returns None otherwise)")
-    stamp = (edge_index.data_ptr(), tuple(edge_index.shape), edge_index._version, int(num_nodes))
+    stamp = (tensor_stamp(edge_index), int(num_nodes))
     cache = {"stamp": stamp, "edge_index": edge_index}
     g0 = g.with_values(g.val)
     g0.symmetric = True

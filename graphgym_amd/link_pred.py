@@ -248,6 +248,9 @@ def run_negatives(plan, seed, offset=0):
                                         ptr(plan.prefix), ptr(plan.slot_base), plan.K,
                                         DIRECTED if plan.directed else UNDIRECTED, int(seed) & _M64,
                                         int(offset) & _M64, ptr(plan.out), _stream()), "mp_sample_non_edges")
+    # plan.out was refilled through its raw pointer: move its version, as copy_ does on the host path, so that a cache
+    # keyed on it (graph.tensor_stamp) sees the new contents
+    torch.autograd.graph.increment_version(plan.out)
     return plan.out
 
 

@@ -17,7 +17,7 @@ import torch
 
 from . import _lib, placement
 from ._lib import check, lib, ptr
-from .graph import CSRGraph, _require_hip, _stream
+from .graph import CSRGraph, _require_hip, _stream, tensor_stamp
 
 
 def _f32c(t, name):
@@ -1911,10 +1911,6 @@ def _offsets_dev(offsets, device):
     return t
 
 
-def _stamp(t):
-    return (t.data_ptr(), tuple(t.shape), t._version)
-
-
 def check_codes(codes, dims, what="codes"):
     """the int32 copy of integer features [R, K] (K = len(dims)) the kernels read, after checking every column k against
     [0, dims[k]) — IndexError as nn.Embedding raises.  One device-to-host read: callers cache the result per batch."""
@@ -1929,6 +1925,7 @@ def check_codes(codes, dims, what="codes"):
     _require_hip(codes, what)
     out = codes.to(torch.int32).contiguous()
     out._mp_checked_dims = tuple(int(v) for v in dims)
+    out._mp_checked_version = out._version        # (an in-place update afterwards voids the check)
     return out
 
 
@@ -1967,10 +1964,10 @@ _ONEHOT_T = {}     # (stamp of the codes tensor, offsets, n_codes) -> (codes, op
 def _code_reduce_fallback(dy, codes, offsets, n_codes):
     """dTable of embed_sum on the transposed one-hot operator: row (off_k + code) <- item row, one entry per item, summed
     by the plan kernel — deterministic (a table row with many items takes the hub path).  offsets: the K host integers.
-    The operator is kept per codes tensor (its address, shape and version: a batch's checked codes are one tensor for all
+    The operator is kept per codes tensor (graph.tensor_stamp: a batch's checked codes are one tensor for all
     steps), for the last few of them."""
     offsets = tuple(int(o) for o in offsets)
-    key = (_stamp(codes), offsets, int(n_codes))
+    key = (tensor_stamp(codes), offsets, int(n_codes))
     hit = _ONEHOT_T.get(key)
     if hit is None:
         if len(_ONEHOT_T) >= 8:
@@ -2044,7 +2041,8 @@ def embed_sum(codes, table, offsets):
     operator, or mp_code_reduce_f32 up to code_reduce_cap() rows)."""
     offsets = [int(o) for o in offsets]
     dims = tuple(b - a for a, b in zip(offsets, offsets[1:] + [table.size(0)]))
-    if getattr(codes, "_mp_checked_dims", None) != dims or codes.dtype != torch.int32:
+    if getattr(codes, "_mp_checked_dims", None) != dims or codes.dtype != torch.int32 \
+            or getattr(codes, "_mp_checked_version", None) != codes._version:
         codes = check_codes(codes, dims)
     if table.dtype != torch.float32:
         raise TypeError(f"embed_sum is float32 only: table is {table.dtype}")
@@ -2053,9 +2051,10 @@ def embed_sum(codes, table, offsets):
 
 def entry_codes(g, codes):
     """codes [E] int32 per INPUT edge -> per stored entry of g (q of the entry's input edge, -1 for an inserted self
-    loop), with the largest entry code and the smallest input code; cached on g for this codes tensor"""
+    loop), with the largest entry code and the smallest input code; cached on g for this codes tensor (graph.tensor_stamp)"""
     hit = g.__dict__.get("_entry_codes")
-    if hit is None or hit[0] is not codes:
+    stamp = tensor_stamp(codes)                    # (not the tensor's identity: an in-place update must be seen)
+    if hit is None or hit[4] != stamp:
         eid = g.eid
         if eid is None:
             raise ValueError("spmm_code needs a graph that knows the input position of its entries (CSRGraph.eid)")
@@ -2066,7 +2065,7 @@ def entry_codes(g, codes):
         q = torch.where(eid >= 0, q, torch.full_like(q, -1)).to(torch.int32).contiguous()
         top = int(q.max().item()) if g.nnz else -1
         low = int(codes.min().item()) if codes.numel() else 0
-        hit = (codes, q, top, low)
+        hit = (codes, q, top, low, stamp)
         g.__dict__["_entry_codes"] = hit
     return hit[1], hit[2], hit[3]
 
@@ -2109,15 +2108,15 @@ def _op_spmm_code_bwd_raw(dy: Tensor, argmax: Tensor, qe: Tensor, graph: int, re
 
 def _entry_reduce_fallback(dy, g, qe, w, reduce, n_codes):
     """dTable of spmm_code (sum / mean) on the transposed one-hot operator of the entries: row q_e <- the entry's row,
-    value w_e, entries without a code left out; cached on g (the op's graph handle names it) for this qe by address,
-    shape and version"""
+    value w_e, entries without a code left out; cached on g (the op's graph handle names it) for this qe by
+    graph.tensor_stamp"""
     cache = g.__dict__.setdefault("_code_onehot_t", {})
     hit = cache.get((reduce, n_codes))
-    if hit is None or hit[2] != _stamp(qe):
+    if hit is None or hit[2] != tensor_stamp(qe):
         keep = torch.nonzero(qe >= 0).view(-1)
         ei = torch.stack([g.row_ids().long()[keep], qe.long()[keep]])
         op = CSRGraph.from_edge_index(ei, n_codes, None if w is None else w[keep], num_cols=max(g.num_nodes, 1))
-        hit = cache[(reduce, n_codes)] = (qe, op, _stamp(qe))
+        hit = cache[(reduce, n_codes)] = (qe, op, tensor_stamp(qe))
     return torch.ops.mp.spmm_raw(dy, hit[1].handle, 0, _lib.SUM, None, 0.0, None, False, False)[0]
 
 
