@@ -10,10 +10,10 @@ import types
 
 import torch
 
-from ._lib import EngineError, check, lib, ptr
+from ._lib import EngineError, K, check, lib, ptr
 from .graph import CSRGraph, _require_hip, _stream
 
-FLAG_CSR, FLAG_CSR_SELF_LOOPS = 1, 2          # mp_engine.h: MP_EGO_CSR, MP_EGO_CSR_SELF_LOOPS
+FLAG_CSR, FLAG_CSR_SELF_LOOPS = K["MP_EGO_CSR"], K["MP_EGO_CSR_SELF_LOOPS"]
 BFS_MAX_NODES = 1 << 16                       # mp_hop_distances: the search's bitmaps live in LDS
 _I32_MAX = 2 ** 31 - 1
 

@@ -4,11 +4,12 @@ import ctypes as C
 
 import torch
 
-from ._lib import ALLOC_FN, FREE_FN, EgoResult, EngineError, check, lib, ptr
+from ._lib import ALLOC_FN, FREE_FN, EgoResult, EngineError, K, check, lib, ptr
 from .graph import CSRGraph, _require_hip, _stream, tensor_stamp  # noqa: F401
 
-TAG_SCRATCH, TAG_EDGES, TAG_ORIG, TAG_EGO_OF, TAG_ROWPTR, TAG_COL, TAG_EID = range(7)
-FLAG_CSR, FLAG_CSR_SELF_LOOPS = 1, 2
+TAG_SCRATCH, TAG_EDGES, TAG_ORIG, TAG_EGO_OF, TAG_ROWPTR, TAG_COL, TAG_EID = (
+    K["MP_EGO_TAG_" + t] for t in "SCRATCH EDGES ORIG EGO_OF ROWPTR COL EID".split())
+FLAG_CSR, FLAG_CSR_SELF_LOOPS = K["MP_EGO_CSR"], K["MP_EGO_CSR_SELF_LOOPS"]
 last_stats = {}          # the last call's sizes (bench / tests read them): nodes, edges, candidates, scratch_peak_bytes
 
 

@@ -19,10 +19,11 @@ import types
 import numpy as np
 import torch
 
+from . import _lib
 from ._lib import check, lib, ptr
 from .graph import CSRGraph, _stream
 
-UNDIRECTED, DIRECTED = 0, 1                   # mp_engine.h: MP_PAIRS_UNDIRECTED, MP_PAIRS_DIRECTED
+UNDIRECTED, DIRECTED = _lib.K["MP_PAIRS_UNDIRECTED"], _lib.K["MP_PAIRS_DIRECTED"]
 ROUNDS = 6                                    # link.hip: kFeistelRounds
 _M64 = (1 << 64) - 1
 _GOLDEN = 0x9E3779B97F4A7C15

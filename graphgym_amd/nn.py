@@ -19,7 +19,7 @@ import torch.nn.functional as F
 from torch.library import custom_op, register_autograd
 
 from . import placement
-from ._lib import check, lib, ptr
+from ._lib import K, check, lib, ptr
 from .graph import _require_hip, _stream
 
 Tensor = torch.Tensor
@@ -130,7 +130,7 @@ register_autograd("mp::bn_act", _bn_backward, setup_context=_bn_setup)
 # Behind a last layer built with has_act=False the block computes act(x + BN(h)) or act(cat(x, BN(h))).  As separate
 # passes that is BN statistics, BN apply, add / cat, activation: 8 N d elements moved (8 N d + 4 N d_skip for cat); the
 # engine's apply pass takes the skip operand and the activation along: 4 N d, or 3 N d + 2 N d_skip.
-SKIP_SUM, SKIP_CONCAT = 0, 1            # MP_BN_SKIP_SUM / MP_BN_SKIP_CONCAT of include/mp_engine.h
+SKIP_SUM, SKIP_CONCAT = K["MP_BN_SKIP_SUM"], K["MP_BN_SKIP_CONCAT"]
 _SKIP_MODES = {"sum": SKIP_SUM, "skipsum": SKIP_SUM, "concat": SKIP_CONCAT, "skipconcat": SKIP_CONCAT,
                SKIP_SUM: SKIP_SUM, SKIP_CONCAT: SKIP_CONCAT}
 
@@ -287,8 +287,8 @@ register_autograd("mp::bn_skip_act", _bn_skip_backward, setup_context=_bn_skip_s
 # The unfused composition moves 5 N d elements forward (statistics, BN apply, activation) and 8 N d backward, and keeps
 # x AND the BatchNorm's output for the backward; with the activation in the apply pass it is 3 N d and 5 N d, and x
 # alone is kept: the backward recomputes the pre-activation from x (csrc/bn.hip, csrc/act.h).
-# MP_ACT_* of include/mp_engine.h
-ACT_NONE, ACT_RELU, ACT_LRELU, ACT_PRELU, ACT_ELU, ACT_SELU, ACT_SILU = range(7)
+ACT_NONE, ACT_RELU, ACT_LRELU, ACT_PRELU, ACT_ELU, ACT_SELU, ACT_SILU = (
+    K["MP_ACT_" + a] for a in "NONE RELU LRELU PRELU ELU SELU SILU".split())
 
 
 def act_spec(module):

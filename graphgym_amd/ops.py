@@ -150,7 +150,7 @@ def _raw_dense_fused(P, W, Q, W_id, bias, relu):
         st = L.mp_dense_fused_f32(ptr(P), P.stride(0), ptr(Wc), ptr(Q), Q.stride(0) if Q is not None else 0,
                                   ptr(Wi), ptr(b), _lib.ACT_RELU if relu else _lib.ACT_NONE, ptr(out),
                                   out.stride(0), M, F, d, _stream())
-    if st in (2, 5):
+    if st in (_lib.MP_ERR_UNSUPPORTED, _lib.MP_ERR_ALIGNMENT):
         return None
     check(st, "mp_dense_fused_f32")
     return out
@@ -308,7 +308,7 @@ def _launch_dense_wgrad(P, G, Y=None, want_bias=False, want_gm=False, gm_out=Non
             name, st = "mp_dense_wgrad_relu_f32", L.mp_dense_wgrad_relu_f32(
                 ptr(P), P.stride(0), ptr(G), G.stride(0), ptr(Y), Y.stride(0), ptr(gm),
                 gm.stride(0) if gm is not None else 0, *tail)
-    if st in (2, 5):
+    if st in (_lib.MP_ERR_UNSUPPORTED, _lib.MP_ERR_ALIGNMENT):
         return None
     check(st, name)
     return out, db, gm
