@@ -1,5 +1,5 @@
-// Integer helpers shared by the keyed samplers (link.hip: negative sampling; sample.hip: mini-batch subgraph samplers)
-// and the keyed dropout mask (bn_drop.hip).
+// Integer helpers shared by the keyed samplers (link.hip: negative sampling; sample.hip: mini-batch subgraph samplers;
+// centrality.hip: one-hot ids) and the keyed dropout mask (bn_drop.hip).
 // Integer mixing only: a draw is a pure function of its key, never of the launch geometry.
 #pragma once
 #include "common.h"
@@ -49,6 +49,44 @@ __device__ __forceinline__ void drop_keep(const DropKey& k, int64_t r, int c0, b
   }
 }
 
+// ---- the keyed bijection (link.hip: ranks of non-edges; centrality.hip: one-hot ids) -------------------------------------
+// perm(i) on [0, C): a balanced Feistel network on 2b bits, b = max(1, ceil(bits(C - 1) / 2)), walked until the value is
+// below C (cycle walking: the domain is below 4 C, fewer than 4 encryptions on average, and the walk from a start below
+// C always returns below C because the network is a bijection).  The round keys come from (seed, offset, g).  The caller
+// guarantees 0 <= i < C: a walk from a start outside the domain need not end.
+constexpr int kFeistelRounds = 6;
+
+__device__ __forceinline__ uint32_t feistel_round(uint32_t half, uint32_t key) {      // (the murmur3 finaliser)
+  uint32_t x = half + key;
+  x ^= x >> 16; x *= 0x85EBCA6Bu;
+  x ^= x >> 13; x *= 0xC2B2AE35u;
+  return x ^ (x >> 16);
+}
+
+__device__ __forceinline__ uint64_t keyed_perm(uint64_t seed, uint64_t offset, uint64_t g, uint64_t i, int64_t C) {
+  uint64_t h = mix64(seed + kGolden);
+  h = mix64((h ^ offset) + kGolden);
+  h = mix64((h ^ g) + kGolden);
+  uint32_t key[kFeistelRounds];
+#pragma unroll
+  for (int k = 0; k < kFeistelRounds; ++k) key[k] = (uint32_t)(mix64(h + (uint64_t)(k + 1) * kGolden) >> 32);
+  const int bits = C > 1 ? 64 - __builtin_clzll((uint64_t)(C - 1)) : 0;
+  const int b = bits > 1 ? (bits + 1) >> 1 : 1;
+  const uint32_t mask = b >= 32 ? 0xFFFFFFFFu : ((1u << b) - 1u);
+  uint64_t x = i;
+  do {
+    uint32_t L = (uint32_t)(x >> b), R = (uint32_t)x & mask;
+#pragma unroll
+    for (int k = 0; k < kFeistelRounds; ++k) {
+      const uint32_t t = L ^ (feistel_round(R, key[k]) & mask);
+      L = R;
+      R = t;
+    }
+    x = ((uint64_t)L << b) | R;
+  } while (x >= (uint64_t)C);
+  return x;
+}
+
 // first index in [lo, hi) whose value is above key
 template <class T>
 __device__ __forceinline__ int64_t upper_bound(const T* __restrict__ a, int64_t lo, int64_t hi, int64_t key) {
@@ -57,6 +95,12 @@ __device__ __forceinline__ int64_t upper_bound(const T* __restrict__ a, int64_t 
     if ((int64_t)a[mid] <= key) lo = mid + 1; else hi = mid;
   }
   return lo;
+}
+
+// the graph (or the slot range) that holds x: the last g in [0, G) with ptr[g] <= x
+__device__ __forceinline__ int64_t range_of(const int64_t* __restrict__ ptr, int64_t G, int64_t x) {
+  int64_t g = upper_bound(ptr, 0, G + 1, x) - 1;
+  return g < 0 ? 0 : (g >= G ? G - 1 : g);
 }
 
 }  // namespace mp

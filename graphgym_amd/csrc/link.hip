@@ -21,24 +21,9 @@
 //   4. undirected: (r, c), r < c; directed: (c, r) as (src, dst).
 // Sample i of graph g depends on (seed, offset, g, i) and the graph alone, never on the launch geometry.
 #include "common.h"
-#include "draws.h"       // mix64, kGolden, upper_bound
+#include "draws.h"       // keyed_perm, upper_bound
 
 namespace mp {
-
-constexpr int kFeistelRounds = 6;
-
-__device__ __forceinline__ uint32_t feistel_round(uint32_t half, uint32_t key) {      // (the murmur3 finaliser)
-  uint32_t x = half + key;
-  x ^= x >> 16; x *= 0x85EBCA6Bu;
-  x ^= x >> 13; x *= 0xC2B2AE35u;
-  return x ^ (x >> 16);
-}
-
-// the graph (or the slot range) that holds x: the last g in [0, G) with ptr[g] <= x
-__device__ __forceinline__ int64_t range_of(const int64_t* __restrict__ ptr, int64_t G, int64_t x) {
-  int64_t g = upper_bound(ptr, 0, G + 1, x) - 1;
-  return g < 0 ? 0 : (g >= G ? G - 1 : g);
-}
 
 // is r stored in its own row [rs, re)?
 __device__ __forceinline__ bool has_diagonal(const int32_t* __restrict__ col, int64_t rs, int64_t re, int64_t r) {
@@ -83,27 +68,8 @@ __global__ __launch_bounds__(kBlock) void sample_non_edges_kernel(
     out[K + slot] = -1;
     return;
   }
-  // 1. the keyed bijection
-  uint64_t h = mix64(seed + kGolden);
-  h = mix64((h ^ offset) + kGolden);
-  h = mix64((h ^ (uint64_t)g) + kGolden);
-  uint32_t key[kFeistelRounds];
-#pragma unroll
-  for (int k = 0; k < kFeistelRounds; ++k) key[k] = (uint32_t)(mix64(h + (uint64_t)(k + 1) * kGolden) >> 32);
-  const int bits = C > 1 ? 64 - __builtin_clzll((uint64_t)(C - 1)) : 0;
-  const int b = bits > 1 ? (bits + 1) >> 1 : 1;
-  const uint32_t mask = b >= 32 ? 0xFFFFFFFFu : ((1u << b) - 1u);
-  uint64_t x = i;
-  do {
-    uint32_t L = (uint32_t)(x >> b), R = (uint32_t)x & mask;
-#pragma unroll
-    for (int k = 0; k < kFeistelRounds; ++k) {
-      const uint32_t t = L ^ (feistel_round(R, key[k]) & mask);
-      L = R;
-      R = t;
-    }
-    x = ((uint64_t)L << b) | R;
-  } while (x >= (uint64_t)C);
+  // 1. the keyed bijection (draws.h)
+  const uint64_t x = keyed_perm(seed, offset, (uint64_t)g, i, C);
   // 2. rank -> row: the first r of [lo, hi) with prefix[r + 1] above the rank
   const int64_t target = p0 + (int64_t)x;
   int64_t r = upper_bound(prefix, lo + 1, hi + 1, target) - 1;

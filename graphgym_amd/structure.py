@@ -1,6 +1,7 @@
 """GraphGym's structural labels and features on the GPU: the raw quantities of graphgym/models/feature_augment.py:51-107
-(one networkx call per node or graph in the reference) through mp_csr_triangles and mp_hop_sums (csrc/structure.hip),
-and the dataset-wide representation of :134-310 (binning, one-hot, position) in plain torch.
+(one networkx call per node or graph in the reference) through mp_csr_triangles and mp_hop_sums (csrc/structure.hip)
+and mp_struct_pagerank, mp_struct_betweenness and mp_struct_onehot (csrc/centrality.hip), and the dataset-wide
+representation of :134-310 (binning, one-hot, position) in plain torch.
 
     tensors, feat_dims, label_dim = augment(base, graph_ptr, ["node_degree"], [8],
                                             label="node_clustering_coefficient", label_dim=10)
@@ -10,22 +11,28 @@ and the dataset-wide representation of :134-310 (binning, one-hot, position) in 
 them (default: one graph).  The reference's datasets are undirected nx.Graphs: every raw quantity requires
 base.is_symmetric(run=True) — the stored operator equals its transpose and stores no (r, c) twice — and raises
 ValueError otherwise (networkx's directed clustering and path definitions are other formulas).  The kernels return exact
-integers; the quotients are one float64 division each, on the device, so they equal networkx's bit for bit.
+integers; the quotients are one float64 division each, on the device, so they equal networkx's bit for bit.  PageRank
+and betweenness are float64 sums in an order of their own: they agree with networkx within rounding (the bounds are in
+DESIGN.md 4.21), reproduce bit for bit, and do not depend on the batch a graph is computed in.
 
 The representation functions take any tensors, CPU ones included."""
+import numpy as np
 import torch
 
+from . import _lib_structure as LS
 from ._lib import EngineError, check, lib, ptr
 from .edge_nets import BFS_MAX_NODES, _check_ids, _graph_ptr
 from .graph import _require_hip, _stream
 
-NODE_KEYS = ("node_degree", "node_path_len", "node_clustering_coefficient", "node_identity", "node_const")
+# node_onehot and node_pagerank are features, and node_pagerank a label, of the reference's synthetic design-space grids
+# (run/grids/design/round1.txt:52,72-73,92, round1att.txt, round2.txt:53); edge_path_len is a node quantity the reference
+# files under an edge key (feature_augment.py:65-68 is path_len_fun word for word)
+NODE_KEYS = ("node_degree", "node_path_len", "node_clustering_coefficient", "node_identity", "node_const",
+             "node_pagerank", "node_betweenness_centrality", "node_onehot", "edge_path_len")
 GRAPH_KEYS = ("graph_path_len", "graph_clustering_coefficient")
 SUPPORTED_KEYS = NODE_KEYS + GRAPH_KEYS
-# the reference's other keys (feature_augment.py:109-122): an iterative method defined by its stopping rule, a random
-# permutation, a dense eigensolve, or (edge_path_len) a node quantity filed under an edge key; no config uses them
-UNBUILT_KEYS = ("node_betweenness_centrality", "node_pagerank", "node_onehot", "edge_path_len",
-                "graph_laplacian_spectrum")
+# the reference's last key (feature_augment.py:109-122): a dense eigensolve, with no kernel of this library in it
+UNBUILT_KEYS = ("graph_laplacian_spectrum",)
 BIN_METHODS = ("balanced", "equal_width", "bounded")
 
 
@@ -190,9 +197,147 @@ def node_identity(base, graph_ptr=None, feature_dim=None):
     return compute_identity(edge_index, N, int(feature_dim), batch=batch if N else None)
 
 
-def raw(key, base, graph_ptr=None, feature_dim=None, _cache=None):
+# ---- centralities and one-hot ids (csrc/centrality.hip, include/mp_structure.h) ----------------------------------------
+
+def _sizes_host(gp, what):
+    """the graphs' node counts as a NumPy array: the one read of graph_ptr's differences a call makes"""
+    n = (gp[1:] - gp[:-1]).cpu().numpy()
+    if (n == 0).any():
+        raise ValueError(f"{what}: graph {int(np.flatnonzero(n == 0)[0])} of graph_ptr is empty")
+    return n
+
+
+def _prefix(counts, dev):
+    """[0, counts[0], counts[0] + counts[1], ...] as an int64 tensor on `dev`"""
+    return torch.from_numpy(np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)).to(dev)
+
+
+def _workspace(nbytes, dev):
+    return torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+
+
+def _ws_bytes(entry, *args):
+    import ctypes
+    nb = ctypes.c_size_t(0)
+    check(getattr(LS.lib(), entry)(*args, ctypes.byref(nb)), entry)
+    return nb.value
+
+
+def node_pagerank(base, graph_ptr=None, alpha=0.85, tol=1e-6, max_iter=100, return_iters=False):
+    """float64 [N]: pagerank_fun (feature_augment.py:70-73) — nx.pagerank(G) per graph, restated in float64: from
+    x = 1 / n the step x' = alpha (x A / deg + dsum / n) + (1 - alpha) / n, the result being the x' of the first step
+    with sum |x' - x| < n tol (include/mp_structure.h has the whole statement).  With return_iters also int32 [G], the
+    number of that step.  Every graph stops on its own count, on the device; the call reads graph_ptr's sizes once
+    before it enqueues anything and `iters` once after.  ValueError for a graph that has not stopped after max_iter
+    steps (networkx raises PowerIterationFailedConvergence there)."""
+    _undirected(base, "node_pagerank")
+    gp = _gp(base, graph_ptr)
+    dev, N = base.device, base.num_nodes
+    if N == 0:
+        out, iters = torch.empty(0, dtype=torch.float64, device=dev), torch.empty(0, dtype=torch.int32, device=dev)
+        return (out, iters) if return_iters else out
+    plan = plan_pagerank(base, gp, _sizes_host(gp, "node_pagerank"), alpha, tol, max_iter)
+    run_pagerank(plan)
+    failed = torch.nonzero(plan.iters.cpu() < 0)
+    if failed.numel():
+        raise ValueError(f"node_pagerank: graph {int(failed[0])} has not converged within {int(max_iter)} iterations")
+    return (plan.out, plan.iters) if return_iters else plan.out
+
+
+def plan_pagerank(base, gp, n, alpha=0.85, tol=1e-6, max_iter=100):
+    """the inputs and preallocated outputs of one mp_struct_pagerank call; gp is the checked graph_ptr on the device and
+    n the graphs' sizes on the host"""
+    import types
+    dev, N, G = base.device, base.num_nodes, len(n)
+    chunks = np.where(n > LS.PAGERANK_LDS_NODES, -(-n // LS.PAGERANK_CHUNK), 0)
+    n_chunks = int(chunks.sum())
+    ws = _workspace(_ws_bytes("mp_struct_pagerank_ws_bytes", N, G, n_chunks), dev)
+    return types.SimpleNamespace(base=base, gp=gp, n_chunks=n_chunks, chunk_ptr=_prefix(chunks, dev) if n_chunks else None,
+                                 alpha=float(alpha), tol=float(tol), max_iter=int(max_iter), ws=ws,
+                                 out=torch.empty(N, dtype=torch.float64, device=dev),
+                                 iters=torch.empty(G, dtype=torch.int32, device=dev))
+
+
+def run_pagerank(plan):
+    """one mp_struct_pagerank call on the current stream (no synchronisation)"""
+    b = plan.base
+    with torch.cuda.device(b.device):
+        check(LS.lib().mp_struct_pagerank(ptr(b.rowptr), ptr(b.col), b.num_nodes, b.nnz, ptr(plan.gp),
+                                          plan.gp.numel() - 1, ptr(plan.chunk_ptr), plan.n_chunks, plan.alpha, plan.tol,
+                                          plan.max_iter, ptr(plan.out), ptr(plan.iters), ptr(plan.ws), plan.ws.numel(),
+                                          _stream()), "mp_struct_pagerank")
+
+
+def node_betweenness_centrality(base, graph_ptr=None):
+    """float64 [N]: centrality_fun (feature_augment.py:55-58) — nx.betweenness_centrality(G) per graph: Brandes'
+    algorithm from every node, unweighted, normalised by (n - 1) (n - 2), endpoints left out.  A node no shortest path
+    passes through gets exactly 0.0.  A graph above 65536 nodes is an EngineError, as for hop_sums."""
+    _undirected(base, "node_betweenness_centrality")
+    gp = _gp(base, graph_ptr)
+    if base.num_nodes == 0:
+        return torch.empty(0, dtype=torch.float64, device=base.device)
+    plan = plan_betweenness(base, gp, _sizes_host(gp, "node_betweenness_centrality"))
+    run_betweenness(plan)
+    return plan.out
+
+
+def plan_betweenness(base, gp, n):
+    """the inputs, workspace and preallocated output of one mp_struct_betweenness call"""
+    import types
+    dev, N = base.device, base.num_nodes
+    biggest = int(n.max()) if len(n) else 0
+    if biggest > BFS_MAX_NODES:
+        raise EngineError(f"node_betweenness_centrality: a graph of {biggest} nodes; the search keeps one level, sigma "
+                          f"and delta vector per slice of sources and takes graphs of up to {BFS_MAX_NODES} nodes")
+    slices = -(-n // LS.BETWEENNESS_SLICE)
+    ws = _workspace(_ws_bytes("mp_struct_betweenness_ws_bytes", N, biggest), dev)
+    return types.SimpleNamespace(base=base, gp=gp, biggest=biggest, slice_ptr=_prefix(slices, dev),
+                                 n_slices=int(slices.sum()), ws=ws, out=torch.empty(N, dtype=torch.float64, device=dev))
+
+
+def run_betweenness(plan):
+    """one mp_struct_betweenness call on the current stream (no synchronisation)"""
+    b = plan.base
+    with torch.cuda.device(b.device):
+        check(LS.lib().mp_struct_betweenness(ptr(b.rowptr), ptr(b.col), b.num_nodes, b.nnz, ptr(plan.gp),
+                                             plan.gp.numel() - 1, plan.biggest, ptr(plan.slice_ptr), plan.n_slices,
+                                             ptr(plan.out), ptr(plan.ws), plan.ws.numel(), _stream()),
+              "mp_struct_betweenness")
+
+
+def node_onehot(base, graph_ptr=None, seed=0):
+    """int64 [N]: onehot_fun (feature_augment.py:88-91) — a random permutation of 0 .. n - 1 per graph, where the
+    reference calls torch.randperm: entry i of graph g is perm(i), the keyed bijection of csrc/draws.h with round keys
+    from (seed, g).  It depends on (seed, g, i, n_g) and nothing else; onehot_host restates it."""
+    _undirected(base, "node_onehot")
+    gp = _gp(base, graph_ptr)
+    dev, N = base.device, base.num_nodes
+    if N:
+        _sizes_host(gp, "node_onehot")
+    out = torch.empty(N, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        check(LS.lib().mp_struct_onehot(ptr(gp), gp.numel() - 1, N, int(seed) & ((1 << 64) - 1), ptr(out), _stream()),
+              "mp_struct_onehot")
+    return out
+
+
+def onehot_host(n_list, seed=0):
+    """node_onehot for graphs of n_list nodes, restated in NumPy integers, bit for bit (int64 [sum of n_list])"""
+    from .link_pred import _permute, _round_keys
+    parts = [_permute(np.arange(int(n), dtype=np.uint64), int(n), _round_keys(int(seed), LS.ONEHOT_STREAM, g))
+             for g, n in enumerate(n_list)]
+    return np.concatenate(parts) if parts else np.zeros(0, dtype=np.int64)
+
+
+def edge_path_len(base, graph_ptr=None, _hops=None):
+    """float64 [N]: edge_path_len_fun (feature_augment.py:65-68), which is path_len_fun under an edge key"""
+    return node_path_len(base, graph_ptr, _hops=_hops)
+
+
+def raw(key, base, graph_ptr=None, feature_dim=None, _cache=None, seed=0):
     """the raw quantity the reference files under `key` (feature_augment.py:109-122).  _cache (a dict) carries the
-    kernels' integers from one key to the next: triangles and hop sums are computed once per dataset."""
+    kernels' integers from one key to the next: triangles and hop sums are computed once per dataset.  seed keys
+    node_onehot's permutations."""
     if key not in SUPPORTED_KEYS:
         why = " (in the reference, but not built here)" if key in UNBUILT_KEYS else ""
         raise KeyError(f"{key!r}{why}: supported keys are {', '.join(SUPPORTED_KEYS)}")
@@ -214,8 +359,14 @@ def raw(key, base, graph_ptr=None, feature_dim=None, _cache=None):
         return node_clustering_coefficient(base, tri())
     if key == "graph_clustering_coefficient":
         return graph_clustering_coefficient(base, graph_ptr, tri())
-    if key == "node_path_len":
+    if key in ("node_path_len", "edge_path_len"):
         return node_path_len(base, graph_ptr, _hops=hops())
+    if key == "node_pagerank":
+        return node_pagerank(base, graph_ptr)
+    if key == "node_betweenness_centrality":
+        return node_betweenness_centrality(base, graph_ptr)
+    if key == "node_onehot":
+        return node_onehot(base, graph_ptr, seed)
     if key == "graph_path_len":
         return graph_path_len(base, graph_ptr, hops())
     if key == "node_const":
@@ -312,7 +463,7 @@ def represent(values, dim, method, as_label=False, node_level=True):
 
 
 def augment(base, graph_ptr, features, feature_dims, label=None, label_dim=None, task_type="classification",
-            feature_repr="balanced"):
+            feature_repr="balanced", seed=0):
     """FeatureAugment.augment (feature_augment.py:247-310) for the dataset whose graphs `base` / graph_ptr hold:
     dataset.augment_feature = features, augment_feature_dims = feature_dims, augment_feature_repr = feature_repr,
     augment_label = label, augment_label_dims = label_dim, dataset.task_type = task_type.
@@ -321,7 +472,7 @@ def augment(base, graph_ptr, features, feature_dims, label=None, label_dim=None,
     label (balanced class ids when "classification" in task_type, else the original values), every tensor covering all
     nodes (node keys) or all graphs (graph keys) of the dataset in order.  The actual dimensions are those of the
     representation — the number of bin edges where balanced bins collapse — and None without a label.  Each raw
-    quantity is computed once, also where it is both a feature and the label."""
+    quantity is computed once, also where it is both a feature and the label.  seed keys node_onehot's permutations."""
     features, feature_dims = list(features), list(feature_dims)
     if len(features) != len(feature_dims):
         raise ValueError("features and feature_dims must have the same length")
@@ -334,7 +485,7 @@ def augment(base, graph_ptr, features, feature_dims, label=None, label_dim=None,
     def raw_of(key, dim):
         at = (key, int(dim)) if key == "node_identity" else key
         if at not in raws:
-            raws[at] = raw(key, base, graph_ptr, feature_dim=dim, _cache=cache)
+            raws[at] = raw(key, base, graph_ptr, feature_dim=dim, _cache=cache, seed=seed)
         return raws[at]
 
     for key, dim in zip(features, feature_dims):
