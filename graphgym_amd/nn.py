@@ -8,6 +8,13 @@ HBM-bound passes; torch's own kernel needs 0.5 s per backward call on a [10^7, 2
 of GraphGym's act_dict (and SiLU) rides the same passes through bn_act_module / bn_skip_act(act=...): act_spec says which.
 gnn.dropout between the BatchNorm and the activation rides them too, as a keyed mask that is recomputed and never stored:
 Dropout, dropout_keep_host, bn_act_module / bn_skip_act(drop=...) (csrc/draws.h, csrc/bn_drop.hip).
+
+The 18 BatchNorm ops (torch.ops.mp.bn_*) are six families — bn_act, bn_skip_act, bn_actx, bn_skip_actx, bn_drop_actx,
+bn_drop_skip_actx — of a differentiable op over a *_fwd_raw and a *_bwd_raw op.  As the C entries are adapters onto one
+forward and one backward runner (csrc/bn_kernels.h), the *_raw ops are adapters onto _bn_fwd and _bn_actx_bwd, their fake
+kernels onto _fwd_results and _bwd_results, which also make the real ops' allocations, and the four *actx families share
+one autograd formula (_actx_autograd); bn_bwd_raw and bn_skip_bwd_raw, whose entries take the forward's output, keep
+bodies of their own.  Every launch goes through _bn_launch, which owns the workspace.
 """
 import ctypes as C
 from typing import Optional, Tuple
@@ -25,38 +32,174 @@ from .graph import _require_hip, _stream
 Tensor = torch.Tensor
 
 
-def _bn_ws(N, d, device):
+# ---- the BatchNorm ops: the Python half of csrc/bn_kernels.h (see the module docstring) -------------------------------
+def _bn_launch(entry, size_fn, x, *args):
+    """entry(*args, ws, ws_bytes, stream) on x's device, ws being the workspace that the entry's size function asks for
+    at x's [N, d]: mp_bn_ws_bytes, mp_bn_act_ws_bytes or mp_bn_drop_ws_bytes"""
     nb = C.c_size_t(0)
-    check(lib().mp_bn_ws_bytes(N, d, C.byref(nb)))
-    return torch.empty(nb.value, dtype=torch.uint8, device=device), nb.value
+    with torch.cuda.device(x.device):
+        check(getattr(lib(), size_fn)(x.size(0), x.size(1), C.byref(nb)))
+        ws = torch.empty(nb.value, dtype=torch.uint8, device=x.device)
+        check(getattr(lib(), entry)(*args, ptr(ws), nb.value, _stream()), entry)
+
+
+def _params(weight, bias, slope=None, kind=None):
+    """(gamma, beta, PRELU's slope) as the entries read them: detached and contiguous, None where there is none"""
+    w = None if weight is None else weight.detach().contiguous()
+    b = None if bias is None else bias.detach().contiguous()
+    return w, b, _slope32(slope, kind)
+
+
+def _new32(like, *shape, reads=None):
+    """uninitialised fp32 [*shape] on like's device; with reads, an engine output placed against what its launch reads"""
+    if reads is None:
+        return torch.empty(shape, dtype=torch.float32, device=like.device)
+    return placement.empty_or_torch(shape, like.device, reads=reads, streaming=True)
+
+
+# (forward entry, backward entry, workspace-size function) by (activation kind, skip operand, keyed mask); the entries
+# with the run-time relu flag instead of a kind keep the workspace layout of mp_bn_ws_bytes and their own backward ops
+_BN_ENTRIES = {
+    (False, False, False): ("mp_bn_train_fwd_f32", None, "mp_bn_ws_bytes"),
+    (False, True, False): ("mp_bn_train_fwd_skip_f32", None, "mp_bn_ws_bytes"),
+    (True, False, False): ("mp_bn_train_fwd_act_f32", "mp_bn_train_bwd_act_f32", "mp_bn_act_ws_bytes"),
+    (True, True, False): ("mp_bn_train_fwd_skip_act_f32", "mp_bn_train_bwd_skip_act_f32", "mp_bn_act_ws_bytes"),
+    (True, False, True): ("mp_bn_train_fwd_drop_act_f32", "mp_bn_train_bwd_drop_act_f32", "mp_bn_drop_ws_bytes"),
+    (True, True, True): ("mp_bn_train_fwd_drop_skip_act_f32", "mp_bn_train_bwd_drop_skip_act_f32", "mp_bn_drop_ws_bytes")}
+
+
+def _fwd_results(x, skip=None, mode=None, placed=False):
+    """(out, mean, invstd, var) of every forward op, uninitialised: out [N, d], or [N, d_skip + d] for SKIP_CONCAT.  As
+    it stands the ops' fake kernel; with placed, the real op's allocations (_bn_fwd), so the two cannot disagree"""
+    d = x.size(1)
+    width = d if (skip is None or mode == SKIP_SUM) else skip.size(1) + d
+    reads = None if not placed else (x,) if skip is None else (x, skip)
+    out, mean = _new32(x, x.size(0), width, reads=reads), _new32(x, d)
+    return out, mean, torch.empty_like(mean), torch.empty_like(mean)
+
+
+def _bn_fwd(rows, x, weight, bias, eps, relu=None, act=None, skip=None, mode=None, drop=None):
+    """(out, mean, invstd, unbiased var): the launch of the six *_fwd_raw ops, with exactly one of relu (a bool: the
+    entries with the run-time flag) and act = (kind, param, slope) (the *_act entries), with skip, mode and drop = (T,
+    seed, offset) where the op has them, and rows, its rule for its operands, applied after every refusal.  One list:
+    x, ldx [, skip, ldskip], N, d [, d_skip, mode], gamma, beta, eps, relu | (kind, param, slope) [, T, seed, offset],
+    out, ldo, mean, invstd, var, ws, nb, stream"""
+    assert (relu is None) != (act is None)
+    has_skip = skip is not None
+    kind, param, slope = act or (None, None, None)
+    _require_hip(x, "x")
+    if has_skip:
+        _require_hip(skip, "skip")
+        _check_skip_shapes(x, skip, mode)
+    if act is not None:
+        _check_kind(kind, slope)
+    key = () if drop is None else _drop_args(*drop)
+    entry, _, size_fn = _BN_ENTRIES[act is not None, has_skip, drop is not None]
+    x, skip = rows(x), (rows(skip) if has_skip else None)
+    N, d = x.shape
+    out, mean, invstd, var_u = _fwd_results(x, skip, mode, placed=True)
+    w, b, s = _params(weight, bias, slope, kind)
+    operand, dims = ((ptr(skip), skip.stride(0)), (skip.size(1), mode)) if has_skip else ((), ())
+    activation = (1 if relu else 0,) if act is None else (kind, float(param), ptr(s))
+    _bn_launch(entry, size_fn, x, ptr(x), x.stride(0), *operand, N, d, *dims, ptr(w), ptr(b), float(eps), *activation,
+               *key, ptr(out), out.stride(0), ptr(mean), ptr(invstd), ptr(var_u))
+    return out, mean, invstd, var_u
+
+
+def _bn_actx_bwd(rows, dy, x, weight, bias, slope, mean, invstd, kind, param, want_dslope, skip=None, mode=None,
+                 want_dskip=False, drop=None):
+    """(dx, dgamma, dbeta [, dskip], dslope): the launch of the four *actx_bwd_raw ops; rows, skip, mode, drop as in
+    _bn_fwd, whose argument list it follows with dy, lddy in front, mean, invstd for eps, and for the outputs
+    dx, lddx [, dskip, lddskip], dgamma, dbeta, dslope"""
+    has_skip = skip is not None
+    if has_skip:
+        _check_skip_shapes(x, skip, mode)
+    _check_kind(kind, slope)
+    key = () if drop is None else _drop_args(*drop)
+    _, entry, size_fn = _BN_ENTRIES[True, has_skip, drop is not None]
+    x, skip, dy = rows(x), (rows(skip) if has_skip else None), rows(dy)
+    N, d = x.shape
+    if has_skip and dy.shape != (N, d if mode == SKIP_SUM else skip.size(1) + d):
+        raise ValueError(f"bn_{'' if drop is None else 'drop_'}skip_actx_bwd_raw: dy {tuple(dy.shape)}, x "
+                         f"{tuple(x.shape)}, skip {tuple(skip.shape)}, mode {mode} do not fit")
+    dx, dgamma, dbeta, *dskip, dslope = results = _bwd_results(dy, x, kind, want_dslope, skip, want_dskip, placed=True)
+    operand = dims = dskip_args = ()
+    if has_skip:
+        operand, dims = (ptr(skip), skip.stride(0)), (skip.size(1), mode)
+        dskip_args = (ptr(dskip[0]), dskip[0].stride(0)) if dskip[0].numel() else (None, 0)
+    w, b, s = _params(weight, bias, slope, kind)
+    _bn_launch(entry, size_fn, x, ptr(dy), dy.stride(0), ptr(x), x.stride(0), *operand, N, d, *dims, ptr(w), ptr(b),
+               ptr(mean), ptr(invstd), kind, float(param), ptr(s), *key, ptr(dx), dx.stride(0), *dskip_args,
+               ptr(dgamma), ptr(dbeta), ptr(dslope) if dslope.numel() else None)
+    return results
+
+
+def _bwd_results(dy, x, kind=None, want_dslope=False, skip=None, want_dskip=False, placed=False):
+    """(dx, dgamma, dbeta [, dskip] [, dslope]), uninitialised, of the four *actx_bwd_raw ops and, without kind, skip and
+    dslope, of bn_bwd_raw: the fake kernel as it stands, the real op's allocations with placed (_bn_actx_bwd).  What is
+    not written comes back EMPTY (an operator cannot return None or a view of its input): dskip unless asked for and
+    there is an activation (without one d(skip) is dy, its left slab, itself: the caller takes it), dslope unless asked
+    for and the kind is PRELU"""
+    dx = _new32(x, *x.shape, reads=(dy, x) if placed else None)
+    dgamma, dskip = _new32(x, x.size(1)), ()
+    if skip is not None:
+        write = want_dskip and kind != ACT_NONE
+        dskip = (_new32(x, *skip.shape, reads=(dy, skip) if placed else None) if write else _new32(x, 0),)
+    dslope = () if kind is None else (_new32(x, 1 if (want_dslope and kind == ACT_PRELU) else 0),)
+    return (dx, dgamma, torch.empty_like(dgamma)) + dskip + dslope
+
+
+def _actx_autograd(op, has_skip, has_drop):
+    """setup_context and backward of one of the four differentiable *actx ops, whose inputs are
+    (x [, skip], weight, bias, slope, eps, kind, param [, mode] [, T, seed, offset]); the backward is <op>_bwd_raw"""
+    i = 2 if has_skip else 1                    # inputs[i:] = weight, bias, slope, eps, kind, param [, mode] [, the key]
+    n_inputs = i + 6 + (1 if has_skip else 0) + (3 if has_drop else 0)
+    bwd_raw = getattr(torch.ops.mp, op._name + "_bwd_raw")
+
+    def setup(ctx, inputs, output):
+        weight, bias, slope, _eps, ctx.kind, ctx.param = inputs[i:i + 6]
+        _, mean, invstd, _ = output
+        ctx.mode, ctx.d_skip = (inputs[i + 6], inputs[1].size(1)) if has_skip else (None, None)
+        ctx.drop = tuple(inputs[n_inputs - 3:]) if has_drop else ()
+        ctx.has = (weight is not None, bias is not None, slope is not None)
+        ctx.slope_shape = None if slope is None else slope.shape
+        # x [, skip]: neither the output nor a mask is kept, the backward recomputes the pre-activation from x, the
+        # statistics and the key; skip is kept where bn_skip_act keeps out, as an operand of that recomputation
+        ctx.save_for_backward(*inputs[:i], weight, bias, slope, mean, invstd)
+
+    def backward(ctx, dy, _dmean, _dinvstd, _dvar):
+        x, *skip, w, b, s, mean, invstd = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        need_x, need_skip, need_w, need_b = need[0], has_skip and need[1], need[i], need[i + 1]
+        need_s = need[i + 2] and ctx.kind == ACT_PRELU
+        dx = dgamma = dbeta = dskip = dslope = None
+        none = ctx.kind == ACT_NONE                 # d(skip) is dy itself: nothing is launched for it
+        if need_x or need_w or need_b or need_s or (need_skip and not none):
+            if has_skip:
+                dx, dgamma, dbeta, dskip, dslope = bwd_raw(dy, x, skip[0], w, b, s, mean, invstd, ctx.mode, ctx.kind,
+                                                           ctx.param, *ctx.drop, need_skip, need_s)
+            else:
+                dx, dgamma, dbeta, dslope = bwd_raw(dy, x, w, b, s, mean, invstd, ctx.kind, ctx.param, *ctx.drop, need_s)
+        if need_skip and none:
+            dskip = dy if ctx.mode == SKIP_SUM else dy[:, :ctx.d_skip]
+        grads = (dx if need_x else None,) + ((dskip if need_skip else None,) if has_skip else ()) + (
+            dgamma if (need_w and ctx.has[0]) else None, dbeta if (need_b and ctx.has[1]) else None,
+            dslope.reshape(ctx.slope_shape) if need_s else None)
+        return grads + (None,) * (n_inputs - len(grads))
+
+    op.register_autograd(backward, setup_context=setup)
+
+
+def _cols32(t):
+    """bn_fwd_raw's and bn_bwd_raw's older rule for x: fp32 with unit column stride, whatever the row stride"""
+    return t if (t.dtype == torch.float32 and t.stride(-1) == 1) else t.float().contiguous()
 
 
 @custom_op("mp::bn_fwd_raw", mutates_args=(), device_types="cuda")
 def _op_bn_fwd_raw(x: Tensor, weight: Optional[Tensor], bias: Optional[Tensor], eps: float,
                    relu: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
     """(y, mean, invstd, unbiased var) of BatchNorm1d over the node axis with batch statistics [+ ReLU]"""
-    _require_hip(x, "x")
-    x = x if (x.dtype == torch.float32 and x.stride(-1) == 1) else x.float().contiguous()
-    N, d = x.shape
-    y = placement.empty_or_torch((N, d), x.device, reads=(x,), streaming=True)
-    mean = torch.empty(d, dtype=torch.float32, device=x.device)
-    invstd = torch.empty_like(mean)
-    var_u = torch.empty_like(mean)
-    w = None if weight is None else weight.detach().contiguous()
-    b = None if bias is None else bias.detach().contiguous()
-    with torch.cuda.device(x.device):
-        ws, nb = _bn_ws(N, d, x.device)
-        check(lib().mp_bn_train_fwd_f32(ptr(x), x.stride(0), N, d, ptr(w), ptr(b), float(eps), 1 if relu else 0,
-                                        ptr(y), y.stride(0), ptr(mean), ptr(invstd), ptr(var_u), ptr(ws), nb,
-                                        _stream()), "mp_bn_train_fwd_f32")
-    return y, mean, invstd, var_u
-
-
-@_op_bn_fwd_raw.register_fake
-def _(x, weight, bias, eps, relu):
-    d = x.size(1)
-    return (x.new_empty(x.shape, dtype=torch.float32), x.new_empty((d,), dtype=torch.float32),
-            x.new_empty((d,), dtype=torch.float32), x.new_empty((d,), dtype=torch.float32))
+    return _bn_fwd(_cols32, x, weight, bias, eps, relu=relu)
 
 
 @custom_op("mp::bn_bwd_raw", mutates_args=(), device_types="cuda")
@@ -65,33 +208,19 @@ def _op_bn_bwd_raw(dy: Tensor, y: Optional[Tensor], x: Tensor, weight: Optional[
                    relu_from_x: bool = False) -> Tuple[Tensor, Tensor, Tensor]:
     """(dx, dgamma, dbeta); y given = the forward's ReLU output (its mask is applied to dy on the fly); relu_from_x:
     the mask is recomputed from x, weight, bias, mean, invstd instead (mp_bn_train_bwd_relu_f32: y is not read)"""
-    x = x if (x.dtype == torch.float32 and x.stride(-1) == 1) else x.float().contiguous()
+    x = _cols32(x)
     N, d = x.shape
     dy = dy.contiguous()
-    dx = placement.empty_or_torch((N, d), x.device, reads=(dy, x), streaming=True)
-    dgamma = torch.empty(d, dtype=torch.float32, device=x.device)
-    dbeta = torch.empty_like(dgamma)
-    w = None if weight is None else weight.detach().contiguous()
-    with torch.cuda.device(x.device):
-        ws, nb = _bn_ws(N, d, x.device)
-        if relu_from_x:
-            b = None if bias is None else bias.detach().contiguous()
-            check(lib().mp_bn_train_bwd_relu_f32(ptr(dy), dy.stride(0), ptr(x), x.stride(0), N, d, ptr(w), ptr(b),
-                                                 ptr(mean), ptr(invstd), ptr(dx), dx.stride(0), ptr(dgamma),
-                                                 ptr(dbeta), ptr(ws), nb, _stream()), "mp_bn_train_bwd_relu_f32")
-        else:
-            check(lib().mp_bn_train_bwd_f32(ptr(dy), dy.stride(0), ptr(y), y.stride(0) if y is not None else 0,
-                                            ptr(x), x.stride(0), N, d, ptr(w), ptr(mean), ptr(invstd), ptr(dx),
-                                            dx.stride(0), ptr(dgamma), ptr(dbeta), ptr(ws), nb, _stream()),
-                  "mp_bn_train_bwd_f32")
+    dx, dgamma, dbeta = _bwd_results(dy, x, placed=True)
+    w, b, _ = _params(weight, bias if relu_from_x else None)
+    if relu_from_x:
+        _bn_launch("mp_bn_train_bwd_relu_f32", "mp_bn_ws_bytes", x, ptr(dy), dy.stride(0), ptr(x), x.stride(0), N, d,
+                   ptr(w), ptr(b), ptr(mean), ptr(invstd), ptr(dx), dx.stride(0), ptr(dgamma), ptr(dbeta))
+    else:
+        _bn_launch("mp_bn_train_bwd_f32", "mp_bn_ws_bytes", x, ptr(dy), dy.stride(0), ptr(y),
+                   y.stride(0) if y is not None else 0, ptr(x), x.stride(0), N, d, ptr(w), ptr(mean), ptr(invstd),
+                   ptr(dx), dx.stride(0), ptr(dgamma), ptr(dbeta))
     return dx, dgamma, dbeta
-
-
-@_op_bn_bwd_raw.register_fake
-def _(dy, y, x, weight, mean, invstd, bias=None, relu_from_x=False):
-    d = x.size(1)
-    return (x.new_empty(x.shape, dtype=torch.float32), x.new_empty((d,), dtype=torch.float32),
-            x.new_empty((d,), dtype=torch.float32))
 
 
 @custom_op("mp::bn_act", mutates_args=(), device_types="cuda")
@@ -99,13 +228,6 @@ def _op_bn_act(x: Tensor, weight: Optional[Tensor], bias: Optional[Tensor], eps:
                relu: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
     """graphgym/models/layer.py:26-35 (BatchNorm1d, then the activation) in training mode: (y, mean, invstd, var)"""
     return torch.ops.mp.bn_fwd_raw(x, weight, bias, eps, relu)
-
-
-@_op_bn_act.register_fake
-def _(x, weight, bias, eps, relu):
-    d = x.size(1)
-    return (x.new_empty(x.shape, dtype=torch.float32), x.new_empty((d,), dtype=torch.float32),
-            x.new_empty((d,), dtype=torch.float32), x.new_empty((d,), dtype=torch.float32))
 
 
 def _bn_setup(ctx, inputs, output):
@@ -150,43 +272,12 @@ def _check_skip_shapes(x, skip, mode):
         raise ValueError(f"SKIP_SUM needs d_skip == d, got {skip.size(1)} and {x.size(1)}")
 
 
-def _skip_fake(x, skip, mode):
-    d = x.size(1)
-    width = d if mode == SKIP_SUM else skip.size(1) + d
-    return (x.new_empty((x.size(0), width), dtype=torch.float32), x.new_empty((d,), dtype=torch.float32),
-            x.new_empty((d,), dtype=torch.float32), x.new_empty((d,), dtype=torch.float32))
-
-
 @custom_op("mp::bn_skip_fwd_raw", mutates_args=(), device_types="cuda")
 def _op_bn_skip_fwd_raw(x: Tensor, skip: Tensor, weight: Optional[Tensor], bias: Optional[Tensor], eps: float,
                         relu: bool, mode: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
     """(out, mean, invstd, unbiased var): out = act(skip + BN(x)) [N, d] (SKIP_SUM) or [act(skip) | act(BN(x))]
     [N, d_skip + d] (SKIP_CONCAT), BN over the node axis with batch statistics; one launch sequence"""
-    _require_hip(x, "x")
-    _require_hip(skip, "skip")
-    _check_skip_shapes(x, skip, mode)
-    x, skip = _rows32(x), _rows32(skip)
-    N, d = x.shape
-    d_skip = skip.size(1)
-    out = placement.empty_or_torch((N, d if mode == SKIP_SUM else d_skip + d), x.device, reads=(x, skip),
-                                   streaming=True)
-    mean = torch.empty(d, dtype=torch.float32, device=x.device)
-    invstd = torch.empty_like(mean)
-    var_u = torch.empty_like(mean)
-    w = None if weight is None else weight.detach().contiguous()
-    b = None if bias is None else bias.detach().contiguous()
-    with torch.cuda.device(x.device):
-        ws, nb = _bn_ws(N, d, x.device)
-        check(lib().mp_bn_train_fwd_skip_f32(ptr(x), x.stride(0), ptr(skip), skip.stride(0), N, d, d_skip, mode, ptr(w),
-                                             ptr(b), float(eps), 1 if relu else 0, ptr(out), out.stride(0), ptr(mean),
-                                             ptr(invstd), ptr(var_u), ptr(ws), nb, _stream()),
-              "mp_bn_train_fwd_skip_f32")
-    return out, mean, invstd, var_u
-
-
-@_op_bn_skip_fwd_raw.register_fake
-def _(x, skip, weight, bias, eps, relu, mode):
-    return _skip_fake(x, skip, mode)
+    return _bn_fwd(_rows32, x, weight, bias, eps, relu=relu, skip=skip, mode=mode)
 
 
 @custom_op("mp::bn_skip_bwd_raw", mutates_args=(), device_types="cuda")
@@ -204,28 +295,22 @@ def _op_bn_skip_bwd_raw(dy: Tensor, out: Optional[Tensor], x: Tensor, weight: Op
     if mode not in (SKIP_SUM, SKIP_CONCAT) or d_skip <= 0 or dy.size(0) != N or (out is not None and out.shape != dy.shape):
         raise ValueError(f"bn_skip_bwd_raw: dy {tuple(dy.shape)}, x {tuple(x.shape)}, mode {mode} do not fit")
     out = None if out is None else _rows32(out)
-    dx = placement.empty_or_torch((N, d), x.device, reads=(dy, x), streaming=True)
-    dgamma = torch.empty(d, dtype=torch.float32, device=x.device)
-    dbeta = torch.empty_like(dgamma)
+    dx, dgamma, dbeta = _bwd_results(dy, x, placed=True)
     dskip = torch.empty(0, dtype=torch.float32, device=x.device)
-    w = None if weight is None else weight.detach().contiguous()
-    with torch.cuda.device(x.device):
-        ws, nb = _bn_ws(N, d, x.device)
-        if mode == SKIP_SUM and out is not None and want_dskip:
-            dskip = placement.empty_or_torch((N, d), x.device, reads=(dy, out), streaming=True)
-            check(lib().mp_bn_train_bwd_skip_f32(ptr(dy), dy.stride(0), ptr(out), out.stride(0), ptr(x), x.stride(0), N,
-                                                 d, ptr(w), ptr(mean), ptr(invstd), ptr(dx), dx.stride(0), ptr(dskip),
-                                                 dskip.stride(0), ptr(dgamma), ptr(dbeta), ptr(ws), nb, _stream()),
-                  "mp_bn_train_bwd_skip_f32")
-        else:
-            dyr = dy if mode == SKIP_SUM else dy[:, d_skip:]
-            yr = out if (out is None or mode == SKIP_SUM) else out[:, d_skip:]
-            check(lib().mp_bn_train_bwd_f32(ptr(dyr), dyr.stride(0), ptr(yr), yr.stride(0) if yr is not None else 0,
-                                            ptr(x), x.stride(0), N, d, ptr(w), ptr(mean), ptr(invstd), ptr(dx),
-                                            dx.stride(0), ptr(dgamma), ptr(dbeta), ptr(ws), nb, _stream()),
-                  "mp_bn_train_bwd_f32")
-            if mode == SKIP_CONCAT and out is not None and want_dskip:
-                dskip = _masked(dy[:, :d_skip], out[:, :d_skip])
+    w, _, _ = _params(weight, None)
+    if mode == SKIP_SUM and out is not None and want_dskip:
+        dskip = placement.empty_or_torch((N, d), x.device, reads=(dy, out), streaming=True)
+        _bn_launch("mp_bn_train_bwd_skip_f32", "mp_bn_ws_bytes", x, ptr(dy), dy.stride(0), ptr(out), out.stride(0),
+                   ptr(x), x.stride(0), N, d, ptr(w), ptr(mean), ptr(invstd), ptr(dx), dx.stride(0), ptr(dskip),
+                   dskip.stride(0), ptr(dgamma), ptr(dbeta))
+    else:
+        dyr = dy if mode == SKIP_SUM else dy[:, d_skip:]
+        yr = out if (out is None or mode == SKIP_SUM) else out[:, d_skip:]
+        _bn_launch("mp_bn_train_bwd_f32", "mp_bn_ws_bytes", x, ptr(dyr), dyr.stride(0), ptr(yr),
+                   yr.stride(0) if yr is not None else 0, ptr(x), x.stride(0), N, d, ptr(w), ptr(mean), ptr(invstd),
+                   ptr(dx), dx.stride(0), ptr(dgamma), ptr(dbeta))
+        if mode == SKIP_CONCAT and out is not None and want_dskip:
+            dskip = _masked(dy[:, :d_skip], out[:, :d_skip])
     return dx, dgamma, dbeta, dskip
 
 
@@ -233,9 +318,7 @@ def _op_bn_skip_bwd_raw(dy: Tensor, out: Optional[Tensor], x: Tensor, weight: Op
 def _(dy, out, x, weight, mean, invstd, mode, want_dskip=True):
     d = x.size(1)
     n_skip = 0 if (out is None or not want_dskip) else (d if mode == SKIP_SUM else dy.size(1) - d)
-    dskip = x.new_empty((x.size(0), n_skip), dtype=torch.float32) if n_skip else x.new_empty((0,), dtype=torch.float32)
-    return (x.new_empty(x.shape, dtype=torch.float32), x.new_empty((d,), dtype=torch.float32),
-            x.new_empty((d,), dtype=torch.float32), dskip)
+    return (_new32(x, *x.shape), _new32(x, d), _new32(x, d), _new32(x, x.size(0), n_skip) if n_skip else _new32(x, 0))
 
 
 def _masked(dy, out):
@@ -249,11 +332,6 @@ def _op_bn_skip_act(x: Tensor, skip: Tensor, weight: Optional[Tensor], bias: Opt
     """graphgym/models/gnn.py:49-60 behind a last layer without activation, in training mode: act(skip + BN(x)) or
     act(cat(skip, BN(x))): (out, mean, invstd, var)"""
     return torch.ops.mp.bn_skip_fwd_raw(x, skip, weight, bias, eps, relu, mode)
-
-
-@_op_bn_skip_act.register_fake
-def _(x, skip, weight, bias, eps, relu, mode):
-    return _skip_fake(x, skip, mode)
 
 
 def _bn_skip_setup(ctx, inputs, output):
@@ -329,43 +407,11 @@ def _slope32(slope, kind):
     return slope.detach().reshape(1).float().contiguous() if kind == ACT_PRELU else None
 
 
-def _bn_act_ws(N, d, device):
-    nb = C.c_size_t(0)
-    check(lib().mp_bn_act_ws_bytes(N, d, C.byref(nb)))
-    return torch.empty(nb.value, dtype=torch.uint8, device=device), nb.value
-
-
-def _stats_fake(x):
-    d = x.size(1)
-    return tuple(x.new_empty((d,), dtype=torch.float32) for _ in range(3))
-
-
 @custom_op("mp::bn_actx_fwd_raw", mutates_args=(), device_types="cuda")
 def _op_bn_actx_fwd_raw(x: Tensor, weight: Optional[Tensor], bias: Optional[Tensor], slope: Optional[Tensor],
                         eps: float, kind: int, param: float) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
     """(y, mean, invstd, unbiased var): y = act(BatchNorm1d(x)) with batch statistics, act = the ACT_* kind"""
-    _require_hip(x, "x")
-    _check_kind(kind, slope)
-    x = _rows32(x)
-    N, d = x.shape
-    y = placement.empty_or_torch((N, d), x.device, reads=(x,), streaming=True)
-    mean = torch.empty(d, dtype=torch.float32, device=x.device)
-    invstd = torch.empty_like(mean)
-    var_u = torch.empty_like(mean)
-    w = None if weight is None else weight.detach().contiguous()
-    b = None if bias is None else bias.detach().contiguous()
-    s = _slope32(slope, kind)
-    with torch.cuda.device(x.device):
-        ws, nb = _bn_act_ws(N, d, x.device)
-        check(lib().mp_bn_train_fwd_act_f32(ptr(x), x.stride(0), N, d, ptr(w), ptr(b), float(eps), kind, float(param),
-                                            ptr(s), ptr(y), y.stride(0), ptr(mean), ptr(invstd), ptr(var_u), ptr(ws),
-                                            nb, _stream()), "mp_bn_train_fwd_act_f32")
-    return y, mean, invstd, var_u
-
-
-@_op_bn_actx_fwd_raw.register_fake
-def _(x, weight, bias, slope, eps, kind, param):
-    return (x.new_empty(x.shape, dtype=torch.float32),) + _stats_fake(x)
+    return _bn_fwd(_rows32, x, weight, bias, eps, act=(kind, param, slope))
 
 
 @custom_op("mp::bn_actx_bwd_raw", mutates_args=(), device_types="cuda")
@@ -374,29 +420,7 @@ def _op_bn_actx_bwd_raw(dy: Tensor, x: Tensor, weight: Optional[Tensor], bias: O
                         want_dslope: bool = True) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
     """(dx, dgamma, dbeta, dslope) of bn_actx_fwd_raw.  The forward's output is not an operand: the pre-activation is
     recomputed from x, weight, bias, mean, invstd.  dslope: [1] for ACT_PRELU with want_dslope, EMPTY otherwise."""
-    _check_kind(kind, slope)
-    x, dy = _rows32(x), _rows32(dy)
-    N, d = x.shape
-    dx = placement.empty_or_torch((N, d), x.device, reads=(dy, x), streaming=True)
-    dgamma = torch.empty(d, dtype=torch.float32, device=x.device)
-    dbeta = torch.empty_like(dgamma)
-    dslope = torch.empty(1 if (kind == ACT_PRELU and want_dslope) else 0, dtype=torch.float32, device=x.device)
-    w = None if weight is None else weight.detach().contiguous()
-    b = None if bias is None else bias.detach().contiguous()
-    s = _slope32(slope, kind)
-    with torch.cuda.device(x.device):
-        ws, nb = _bn_act_ws(N, d, x.device)
-        check(lib().mp_bn_train_bwd_act_f32(ptr(dy), dy.stride(0), ptr(x), x.stride(0), N, d, ptr(w), ptr(b), ptr(mean),
-                                            ptr(invstd), kind, float(param), ptr(s), ptr(dx), dx.stride(0),
-                                            ptr(dgamma), ptr(dbeta), ptr(dslope) if dslope.numel() else None, ptr(ws),
-                                            nb, _stream()), "mp_bn_train_bwd_act_f32")
-    return dx, dgamma, dbeta, dslope
-
-
-@_op_bn_actx_bwd_raw.register_fake
-def _(dy, x, weight, bias, slope, mean, invstd, kind, param, want_dslope=True):
-    return (x.new_empty(x.shape, dtype=torch.float32),) + _stats_fake(x)[:2] + (
-        x.new_empty((1 if (kind == ACT_PRELU and want_dslope) else 0,), dtype=torch.float32),)
+    return _bn_actx_bwd(_rows32, dy, x, weight, bias, slope, mean, invstd, kind, param, want_dslope)
 
 
 @custom_op("mp::bn_actx", mutates_args=(), device_types="cuda")
@@ -406,67 +430,12 @@ def _op_bn_actx(x: Tensor, weight: Optional[Tensor], bias: Optional[Tensor], slo
     return torch.ops.mp.bn_actx_fwd_raw(x, weight, bias, slope, eps, kind, param)
 
 
-@_op_bn_actx.register_fake
-def _(x, weight, bias, slope, eps, kind, param):
-    return (x.new_empty(x.shape, dtype=torch.float32),) + _stats_fake(x)
-
-
-def _bn_actx_setup(ctx, inputs, output):
-    x, weight, bias, slope, eps, kind, param = inputs
-    _, mean, invstd, _ = output
-    ctx.kind, ctx.param = kind, param
-    ctx.has = (weight is not None, bias is not None, slope is not None)
-    ctx.slope_shape = None if slope is None else slope.shape
-    ctx.save_for_backward(x, weight, bias, slope, mean, invstd)      # not y: the backward recomputes it from x
-
-
-def _bn_actx_backward(ctx, dy, _dmean, _dinvstd, _dvar):
-    x, w, b, s, mean, invstd = ctx.saved_tensors
-    need_x, need_w, need_b, need_s = ctx.needs_input_grad[:4]
-    need_s = need_s and ctx.kind == ACT_PRELU
-    if not (need_x or need_w or need_b or need_s):
-        return (None,) * 7
-    dx, dgamma, dbeta, dslope = torch.ops.mp.bn_actx_bwd_raw(dy, x, w, b, s, mean, invstd, ctx.kind, ctx.param, need_s)
-    return (dx if need_x else None, dgamma if (need_w and ctx.has[0]) else None,
-            dbeta if (need_b and ctx.has[1]) else None, dslope.reshape(ctx.slope_shape) if need_s else None,
-            None, None, None)
-
-
-register_autograd("mp::bn_actx", _bn_actx_backward, setup_context=_bn_actx_setup)
-
-
 @custom_op("mp::bn_skip_actx_fwd_raw", mutates_args=(), device_types="cuda")
 def _op_bn_skip_actx_fwd_raw(x: Tensor, skip: Tensor, weight: Optional[Tensor], bias: Optional[Tensor],
                              slope: Optional[Tensor], eps: float, kind: int, param: float,
                              mode: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
     """bn_skip_fwd_raw with the ACT_* kind in place of the ReLU switch"""
-    _require_hip(x, "x")
-    _require_hip(skip, "skip")
-    _check_skip_shapes(x, skip, mode)
-    _check_kind(kind, slope)
-    x, skip = _rows32(x), _rows32(skip)
-    N, d = x.shape
-    d_skip = skip.size(1)
-    out = placement.empty_or_torch((N, d if mode == SKIP_SUM else d_skip + d), x.device, reads=(x, skip),
-                                   streaming=True)
-    mean = torch.empty(d, dtype=torch.float32, device=x.device)
-    invstd = torch.empty_like(mean)
-    var_u = torch.empty_like(mean)
-    w = None if weight is None else weight.detach().contiguous()
-    b = None if bias is None else bias.detach().contiguous()
-    s = _slope32(slope, kind)
-    with torch.cuda.device(x.device):
-        ws, nb = _bn_act_ws(N, d, x.device)
-        check(lib().mp_bn_train_fwd_skip_act_f32(ptr(x), x.stride(0), ptr(skip), skip.stride(0), N, d, d_skip, mode,
-                                                 ptr(w), ptr(b), float(eps), kind, float(param), ptr(s), ptr(out),
-                                                 out.stride(0), ptr(mean), ptr(invstd), ptr(var_u), ptr(ws), nb,
-                                                 _stream()), "mp_bn_train_fwd_skip_act_f32")
-    return out, mean, invstd, var_u
-
-
-@_op_bn_skip_actx_fwd_raw.register_fake
-def _(x, skip, weight, bias, slope, eps, kind, param, mode):
-    return _skip_fake(x, skip, mode)
+    return _bn_fwd(_rows32, x, weight, bias, eps, act=(kind, param, slope), skip=skip, mode=mode)
 
 
 @custom_op("mp::bn_skip_actx_bwd_raw", mutates_args=(), device_types="cuda")
@@ -478,43 +447,8 @@ def _op_bn_skip_actx_bwd_raw(dy: Tensor, x: Tensor, skip: Tensor, weight: Option
     SKIP_SUM: the statistics pass writes dskip = dy * act'(skip + BN(x)) and the apply pass reads it back; without
     want_dskip the apply pass recomputes it.  SKIP_CONCAT: dskip = dy[:, :d_skip] * act'(skip).  dskip comes back EMPTY
     without want_dskip and for ACT_NONE (d(skip) is dy itself: the caller takes it); dslope as in bn_actx_bwd_raw."""
-    _check_skip_shapes(x, skip, mode)
-    _check_kind(kind, slope)
-    x, skip, dy = _rows32(x), _rows32(skip), _rows32(dy)
-    N, d = x.shape
-    d_skip = skip.size(1)
-    if dy.shape != (N, d if mode == SKIP_SUM else d_skip + d):
-        raise ValueError(f"bn_skip_actx_bwd_raw: dy {tuple(dy.shape)}, x {tuple(x.shape)}, skip {tuple(skip.shape)}, "
-                         f"mode {mode} do not fit")
-    dx = placement.empty_or_torch((N, d), x.device, reads=(dy, x), streaming=True)
-    dgamma = torch.empty(d, dtype=torch.float32, device=x.device)
-    dbeta = torch.empty_like(dgamma)
-    dslope = torch.empty(1 if (kind == ACT_PRELU and want_dslope) else 0, dtype=torch.float32, device=x.device)
-    if want_dskip and kind != ACT_NONE:
-        dskip = placement.empty_or_torch((N, d_skip), x.device, reads=(dy, skip), streaming=True)
-    else:
-        dskip = torch.empty(0, dtype=torch.float32, device=x.device)
-    w = None if weight is None else weight.detach().contiguous()
-    b = None if bias is None else bias.detach().contiguous()
-    s = _slope32(slope, kind)
-    with torch.cuda.device(x.device):
-        ws, nb = _bn_act_ws(N, d, x.device)
-        check(lib().mp_bn_train_bwd_skip_act_f32(ptr(dy), dy.stride(0), ptr(x), x.stride(0), ptr(skip), skip.stride(0),
-                                                 N, d, d_skip, mode, ptr(w), ptr(b), ptr(mean), ptr(invstd), kind,
-                                                 float(param), ptr(s), ptr(dx), dx.stride(0),
-                                                 ptr(dskip) if dskip.numel() else None,
-                                                 dskip.stride(0) if dskip.numel() else 0, ptr(dgamma), ptr(dbeta),
-                                                 ptr(dslope) if dslope.numel() else None, ptr(ws), nb, _stream()),
-              "mp_bn_train_bwd_skip_act_f32")
-    return dx, dgamma, dbeta, dskip, dslope
-
-
-@_op_bn_skip_actx_bwd_raw.register_fake
-def _(dy, x, skip, weight, bias, slope, mean, invstd, mode, kind, param, want_dskip=True, want_dslope=True):
-    dskip = (x.new_empty(skip.shape, dtype=torch.float32) if (want_dskip and kind != ACT_NONE)
-             else x.new_empty((0,), dtype=torch.float32))
-    return (x.new_empty(x.shape, dtype=torch.float32),) + _stats_fake(x)[:2] + (
-        dskip, x.new_empty((1 if (kind == ACT_PRELU and want_dslope) else 0,), dtype=torch.float32))
+    return _bn_actx_bwd(_rows32, dy, x, weight, bias, slope, mean, invstd, kind, param, want_dslope, skip=skip,
+                        mode=mode, want_dskip=want_dskip)
 
 
 @custom_op("mp::bn_skip_actx", mutates_args=(), device_types="cuda")
@@ -524,40 +458,6 @@ def _op_bn_skip_actx(x: Tensor, skip: Tensor, weight: Optional[Tensor], bias: Op
     """graphgym/models/gnn.py:49-60 behind a last layer without activation, in training mode, with any cfg.gnn.act:
     act(skip + BN(x)) or act(cat(skip, BN(x))): (out, mean, invstd, var)"""
     return torch.ops.mp.bn_skip_actx_fwd_raw(x, skip, weight, bias, slope, eps, kind, param, mode)
-
-
-@_op_bn_skip_actx.register_fake
-def _(x, skip, weight, bias, slope, eps, kind, param, mode):
-    return _skip_fake(x, skip, mode)
-
-
-def _bn_skip_actx_setup(ctx, inputs, output):
-    x, skip, weight, bias, slope, eps, kind, param, mode = inputs
-    _, mean, invstd, _ = output
-    ctx.kind, ctx.param, ctx.mode, ctx.d_skip = kind, param, mode, skip.size(1)
-    ctx.has = (weight is not None, bias is not None, slope is not None)
-    ctx.slope_shape = None if slope is None else slope.shape
-    # skip is kept where out was: the pre-activation is recomputed from x and skip
-    ctx.save_for_backward(x, skip, weight, bias, slope, mean, invstd)
-
-
-def _bn_skip_actx_backward(ctx, dy, _dmean, _dinvstd, _dvar):
-    x, skip, w, b, s, mean, invstd = ctx.saved_tensors
-    need_x, need_skip, need_w, need_b, need_s = ctx.needs_input_grad[:5]
-    need_s = need_s and ctx.kind == ACT_PRELU
-    dx = dgamma = dbeta = dskip = dslope = None
-    none = ctx.kind == ACT_NONE
-    if need_x or need_w or need_b or need_s or (need_skip and not none):
-        dx, dgamma, dbeta, dskip, dslope = torch.ops.mp.bn_skip_actx_bwd_raw(
-            dy, x, skip, w, b, s, mean, invstd, ctx.mode, ctx.kind, ctx.param, need_skip, need_s)
-    if need_skip and none:
-        dskip = dy if ctx.mode == SKIP_SUM else dy[:, :ctx.d_skip]
-    return (dx if need_x else None, dskip if need_skip else None, dgamma if (need_w and ctx.has[0]) else None,
-            dbeta if (need_b and ctx.has[1]) else None, dslope.reshape(ctx.slope_shape) if need_s else None,
-            None, None, None, None)
-
-
-register_autograd("mp::bn_skip_actx", _bn_skip_actx_backward, setup_context=_bn_skip_actx_setup)
 
 
 # ---- gnn.dropout between the BatchNorm and the activation: a keyed mask (csrc/draws.h, csrc/bn_drop.hip) -------------
@@ -630,11 +530,6 @@ def _op_dropout_keyed(x: Tensor, T: int, seed: int, offset: int) -> Tensor:
     return out
 
 
-@_op_dropout_keyed.register_fake
-def _(x, T, seed, offset):
-    return x.new_empty(x.shape, dtype=torch.float32)
-
-
 def _dropout_keyed_setup(ctx, inputs, output):
     _, ctx.T, ctx.seed, ctx.offset = inputs
 
@@ -647,41 +542,12 @@ def _dropout_keyed_backward(ctx, dy):
 register_autograd("mp::dropout_keyed", _dropout_keyed_backward, setup_context=_dropout_keyed_setup)
 
 
-def _bn_drop_ws(N, d, device):
-    nb = C.c_size_t(0)
-    check(lib().mp_bn_drop_ws_bytes(N, d, C.byref(nb)))
-    return torch.empty(nb.value, dtype=torch.uint8, device=device), nb.value
-
-
 @custom_op("mp::bn_drop_actx_fwd_raw", mutates_args=(), device_types="cuda")
 def _op_bn_drop_actx_fwd_raw(x: Tensor, weight: Optional[Tensor], bias: Optional[Tensor], slope: Optional[Tensor],
                              eps: float, kind: int, param: float, T: int, seed: int,
                              offset: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
     """(y, mean, invstd, unbiased var): y = act(keep * scale * BatchNorm1d(x)) with batch statistics"""
-    _require_hip(x, "x")
-    _check_kind(kind, slope)
-    T, seed_c, off_c = _drop_args(T, seed, offset)
-    x = _rows32(x)
-    N, d = x.shape
-    y = placement.empty_or_torch((N, d), x.device, reads=(x,), streaming=True)
-    mean = torch.empty(d, dtype=torch.float32, device=x.device)
-    invstd = torch.empty_like(mean)
-    var_u = torch.empty_like(mean)
-    w = None if weight is None else weight.detach().contiguous()
-    b = None if bias is None else bias.detach().contiguous()
-    s = _slope32(slope, kind)
-    with torch.cuda.device(x.device):
-        ws, nb = _bn_drop_ws(N, d, x.device)
-        check(lib().mp_bn_train_fwd_drop_act_f32(ptr(x), x.stride(0), N, d, ptr(w), ptr(b), float(eps), kind,
-                                                 float(param), ptr(s), T, seed_c, off_c, ptr(y), y.stride(0), ptr(mean),
-                                                 ptr(invstd), ptr(var_u), ptr(ws), nb, _stream()),
-              "mp_bn_train_fwd_drop_act_f32")
-    return y, mean, invstd, var_u
-
-
-@_op_bn_drop_actx_fwd_raw.register_fake
-def _(x, weight, bias, slope, eps, kind, param, T, seed, offset):
-    return (x.new_empty(x.shape, dtype=torch.float32),) + _stats_fake(x)
+    return _bn_fwd(_rows32, x, weight, bias, eps, act=(kind, param, slope), drop=(T, seed, offset))
 
 
 @custom_op("mp::bn_drop_actx_bwd_raw", mutates_args=(), device_types="cuda")
@@ -691,31 +557,8 @@ def _op_bn_drop_actx_bwd_raw(dy: Tensor, x: Tensor, weight: Optional[Tensor], bi
                              want_dslope: bool = True) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
     """(dx, dgamma, dbeta, dslope) of bn_drop_actx_fwd_raw.  Neither the forward's output nor a mask is an operand: the
     masked pre-activation is recomputed from x, the statistics and the key.  dslope as in bn_actx_bwd_raw."""
-    _check_kind(kind, slope)
-    T, seed_c, off_c = _drop_args(T, seed, offset)
-    x, dy = _rows32(x), _rows32(dy)
-    N, d = x.shape
-    dx = placement.empty_or_torch((N, d), x.device, reads=(dy, x), streaming=True)
-    dgamma = torch.empty(d, dtype=torch.float32, device=x.device)
-    dbeta = torch.empty_like(dgamma)
-    dslope = torch.empty(1 if (kind == ACT_PRELU and want_dslope) else 0, dtype=torch.float32, device=x.device)
-    w = None if weight is None else weight.detach().contiguous()
-    b = None if bias is None else bias.detach().contiguous()
-    s = _slope32(slope, kind)
-    with torch.cuda.device(x.device):
-        ws, nb = _bn_drop_ws(N, d, x.device)
-        check(lib().mp_bn_train_bwd_drop_act_f32(ptr(dy), dy.stride(0), ptr(x), x.stride(0), N, d, ptr(w), ptr(b),
-                                                 ptr(mean), ptr(invstd), kind, float(param), ptr(s), T, seed_c, off_c,
-                                                 ptr(dx), dx.stride(0), ptr(dgamma), ptr(dbeta),
-                                                 ptr(dslope) if dslope.numel() else None, ptr(ws), nb, _stream()),
-              "mp_bn_train_bwd_drop_act_f32")
-    return dx, dgamma, dbeta, dslope
-
-
-@_op_bn_drop_actx_bwd_raw.register_fake
-def _(dy, x, weight, bias, slope, mean, invstd, kind, param, T, seed, offset, want_dslope=True):
-    return (x.new_empty(x.shape, dtype=torch.float32),) + _stats_fake(x)[:2] + (
-        x.new_empty((1 if (kind == ACT_PRELU and want_dslope) else 0,), dtype=torch.float32),)
+    return _bn_actx_bwd(_rows32, dy, x, weight, bias, slope, mean, invstd, kind, param, want_dslope,
+                        drop=(T, seed, offset))
 
 
 @custom_op("mp::bn_drop_actx", mutates_args=(), device_types="cuda")
@@ -727,70 +570,13 @@ def _op_bn_drop_actx(x: Tensor, weight: Optional[Tensor], bias: Optional[Tensor]
     return torch.ops.mp.bn_drop_actx_fwd_raw(x, weight, bias, slope, eps, kind, param, T, seed, offset)
 
 
-@_op_bn_drop_actx.register_fake
-def _(x, weight, bias, slope, eps, kind, param, T, seed, offset):
-    return (x.new_empty(x.shape, dtype=torch.float32),) + _stats_fake(x)
-
-
-def _bn_drop_actx_setup(ctx, inputs, output):
-    x, weight, bias, slope, eps, kind, param, T, seed, offset = inputs
-    _, mean, invstd, _ = output
-    ctx.kind, ctx.param, ctx.drop = kind, param, (T, seed, offset)
-    ctx.has = (weight is not None, bias is not None, slope is not None)
-    ctx.slope_shape = None if slope is None else slope.shape
-    ctx.save_for_backward(x, weight, bias, slope, mean, invstd)      # neither y nor a mask: both are recomputed
-
-
-def _bn_drop_actx_backward(ctx, dy, _dmean, _dinvstd, _dvar):
-    x, w, b, s, mean, invstd = ctx.saved_tensors
-    need_x, need_w, need_b, need_s = ctx.needs_input_grad[:4]
-    need_s = need_s and ctx.kind == ACT_PRELU
-    if not (need_x or need_w or need_b or need_s):
-        return (None,) * 10
-    dx, dgamma, dbeta, dslope = torch.ops.mp.bn_drop_actx_bwd_raw(dy, x, w, b, s, mean, invstd, ctx.kind, ctx.param,
-                                                                  *ctx.drop, need_s)
-    return (dx if need_x else None, dgamma if (need_w and ctx.has[0]) else None,
-            dbeta if (need_b and ctx.has[1]) else None, dslope.reshape(ctx.slope_shape) if need_s else None,
-            None, None, None, None, None, None)
-
-
-register_autograd("mp::bn_drop_actx", _bn_drop_actx_backward, setup_context=_bn_drop_actx_setup)
-
-
 @custom_op("mp::bn_drop_skip_actx_fwd_raw", mutates_args=(), device_types="cuda")
 def _op_bn_drop_skip_actx_fwd_raw(x: Tensor, skip: Tensor, weight: Optional[Tensor], bias: Optional[Tensor],
                                   slope: Optional[Tensor], eps: float, kind: int, param: float, mode: int, T: int,
                                   seed: int, offset: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
     """bn_skip_actx_fwd_raw with the keyed mask on the BatchNorm term, before the skip operand"""
-    _require_hip(x, "x")
-    _require_hip(skip, "skip")
-    _check_skip_shapes(x, skip, mode)
-    _check_kind(kind, slope)
-    T, seed_c, off_c = _drop_args(T, seed, offset)
-    x, skip = _rows32(x), _rows32(skip)
-    N, d = x.shape
-    d_skip = skip.size(1)
-    out = placement.empty_or_torch((N, d if mode == SKIP_SUM else d_skip + d), x.device, reads=(x, skip),
-                                   streaming=True)
-    mean = torch.empty(d, dtype=torch.float32, device=x.device)
-    invstd = torch.empty_like(mean)
-    var_u = torch.empty_like(mean)
-    w = None if weight is None else weight.detach().contiguous()
-    b = None if bias is None else bias.detach().contiguous()
-    s = _slope32(slope, kind)
-    with torch.cuda.device(x.device):
-        ws, nb = _bn_drop_ws(N, d, x.device)
-        check(lib().mp_bn_train_fwd_drop_skip_act_f32(ptr(x), x.stride(0), ptr(skip), skip.stride(0), N, d, d_skip, mode,
-                                                      ptr(w), ptr(b), float(eps), kind, float(param), ptr(s), T, seed_c,
-                                                      off_c, ptr(out), out.stride(0), ptr(mean), ptr(invstd),
-                                                      ptr(var_u), ptr(ws), nb, _stream()),
-              "mp_bn_train_fwd_drop_skip_act_f32")
-    return out, mean, invstd, var_u
-
-
-@_op_bn_drop_skip_actx_fwd_raw.register_fake
-def _(x, skip, weight, bias, slope, eps, kind, param, mode, T, seed, offset):
-    return _skip_fake(x, skip, mode)
+    return _bn_fwd(_rows32, x, weight, bias, eps, act=(kind, param, slope), skip=skip, mode=mode,
+                   drop=(T, seed, offset))
 
 
 @custom_op("mp::bn_drop_skip_actx_bwd_raw", mutates_args=(), device_types="cuda")
@@ -801,45 +587,8 @@ def _op_bn_drop_skip_actx_bwd_raw(dy: Tensor, x: Tensor, skip: Tensor, weight: O
                                   want_dslope: bool = True) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
     """(dx, dgamma, dbeta, dskip, dslope) of bn_drop_skip_actx_fwd_raw from x, skip and the key.  dskip = dy * act'(.) is
     NOT masked; the gradient into the BatchNorm is.  dskip and dslope come back EMPTY as in bn_skip_actx_bwd_raw."""
-    _check_skip_shapes(x, skip, mode)
-    _check_kind(kind, slope)
-    T, seed_c, off_c = _drop_args(T, seed, offset)
-    x, skip, dy = _rows32(x), _rows32(skip), _rows32(dy)
-    N, d = x.shape
-    d_skip = skip.size(1)
-    if dy.shape != (N, d if mode == SKIP_SUM else d_skip + d):
-        raise ValueError(f"bn_drop_skip_actx_bwd_raw: dy {tuple(dy.shape)}, x {tuple(x.shape)}, skip "
-                         f"{tuple(skip.shape)}, mode {mode} do not fit")
-    dx = placement.empty_or_torch((N, d), x.device, reads=(dy, x), streaming=True)
-    dgamma = torch.empty(d, dtype=torch.float32, device=x.device)
-    dbeta = torch.empty_like(dgamma)
-    dslope = torch.empty(1 if (kind == ACT_PRELU and want_dslope) else 0, dtype=torch.float32, device=x.device)
-    if want_dskip and kind != ACT_NONE:
-        dskip = placement.empty_or_torch((N, d_skip), x.device, reads=(dy, skip), streaming=True)
-    else:
-        dskip = torch.empty(0, dtype=torch.float32, device=x.device)
-    w = None if weight is None else weight.detach().contiguous()
-    b = None if bias is None else bias.detach().contiguous()
-    s = _slope32(slope, kind)
-    with torch.cuda.device(x.device):
-        ws, nb = _bn_drop_ws(N, d, x.device)
-        check(lib().mp_bn_train_bwd_drop_skip_act_f32(ptr(dy), dy.stride(0), ptr(x), x.stride(0), ptr(skip),
-                                                      skip.stride(0), N, d, d_skip, mode, ptr(w), ptr(b), ptr(mean),
-                                                      ptr(invstd), kind, float(param), ptr(s), T, seed_c, off_c, ptr(dx),
-                                                      dx.stride(0), ptr(dskip) if dskip.numel() else None,
-                                                      dskip.stride(0) if dskip.numel() else 0, ptr(dgamma), ptr(dbeta),
-                                                      ptr(dslope) if dslope.numel() else None, ptr(ws), nb, _stream()),
-              "mp_bn_train_bwd_drop_skip_act_f32")
-    return dx, dgamma, dbeta, dskip, dslope
-
-
-@_op_bn_drop_skip_actx_bwd_raw.register_fake
-def _(dy, x, skip, weight, bias, slope, mean, invstd, mode, kind, param, T, seed, offset, want_dskip=True,
-      want_dslope=True):
-    dskip = (x.new_empty(skip.shape, dtype=torch.float32) if (want_dskip and kind != ACT_NONE)
-             else x.new_empty((0,), dtype=torch.float32))
-    return (x.new_empty(x.shape, dtype=torch.float32),) + _stats_fake(x)[:2] + (
-        dskip, x.new_empty((1 if (kind == ACT_PRELU and want_dslope) else 0,), dtype=torch.float32))
+    return _bn_actx_bwd(_rows32, dy, x, weight, bias, slope, mean, invstd, kind, param, want_dslope, skip=skip,
+                        mode=mode, want_dskip=want_dskip, drop=(T, seed, offset))
 
 
 @custom_op("mp::bn_drop_skip_actx", mutates_args=(), device_types="cuda")
@@ -851,37 +600,37 @@ def _op_bn_drop_skip_actx(x: Tensor, skip: Tensor, weight: Optional[Tensor], bia
     return torch.ops.mp.bn_drop_skip_actx_fwd_raw(x, skip, weight, bias, slope, eps, kind, param, mode, T, seed, offset)
 
 
-@_op_bn_drop_skip_actx.register_fake
-def _(x, skip, weight, bias, slope, eps, kind, param, mode, T, seed, offset):
-    return _skip_fake(x, skip, mode)
-
-
-def _bn_drop_skip_actx_setup(ctx, inputs, output):
-    x, skip, weight, bias, slope, eps, kind, param, mode, T, seed, offset = inputs
-    _, mean, invstd, _ = output
-    ctx.kind, ctx.param, ctx.mode, ctx.d_skip, ctx.drop = kind, param, mode, skip.size(1), (T, seed, offset)
-    ctx.has = (weight is not None, bias is not None, slope is not None)
-    ctx.slope_shape = None if slope is None else slope.shape
-    ctx.save_for_backward(x, skip, weight, bias, slope, mean, invstd)
-
-
-def _bn_drop_skip_actx_backward(ctx, dy, _dmean, _dinvstd, _dvar):
-    x, skip, w, b, s, mean, invstd = ctx.saved_tensors
-    need_x, need_skip, need_w, need_b, need_s = ctx.needs_input_grad[:5]
-    need_s = need_s and ctx.kind == ACT_PRELU
-    dx = dgamma = dbeta = dskip = dslope = None
-    none = ctx.kind == ACT_NONE
-    if need_x or need_w or need_b or need_s or (need_skip and not none):
-        dx, dgamma, dbeta, dskip, dslope = torch.ops.mp.bn_drop_skip_actx_bwd_raw(
-            dy, x, skip, w, b, s, mean, invstd, ctx.mode, ctx.kind, ctx.param, *ctx.drop, need_skip, need_s)
-    if need_skip and none:
-        dskip = dy if ctx.mode == SKIP_SUM else dy[:, :ctx.d_skip]
-    return (dx if need_x else None, dskip if need_skip else None, dgamma if (need_w and ctx.has[0]) else None,
-            dbeta if (need_b and ctx.has[1]) else None, dslope.reshape(ctx.slope_shape) if need_s else None,
-            None, None, None, None, None, None, None)
-
-
-register_autograd("mp::bn_drop_skip_actx", _bn_drop_skip_actx_backward, setup_context=_bn_drop_skip_actx_setup)
+# the fake kernels, one explicit line per signature (a differentiable op has its forward's), and the shared autograd
+for _op in (_op_bn_fwd_raw, _op_bn_act):
+    _op.register_fake(lambda x, weight, bias, eps, relu: _fwd_results(x))
+for _op in (_op_bn_skip_fwd_raw, _op_bn_skip_act):
+    _op.register_fake(lambda x, skip, weight, bias, eps, relu, mode: _fwd_results(x, skip, mode))
+for _op in (_op_bn_actx_fwd_raw, _op_bn_actx):
+    _op.register_fake(lambda x, weight, bias, slope, eps, kind, param: _fwd_results(x))
+for _op in (_op_bn_skip_actx_fwd_raw, _op_bn_skip_actx):
+    _op.register_fake(lambda x, skip, weight, bias, slope, eps, kind, param, mode: _fwd_results(x, skip, mode))
+for _op in (_op_bn_drop_actx_fwd_raw, _op_bn_drop_actx):
+    _op.register_fake(lambda x, weight, bias, slope, eps, kind, param, T, seed, offset: _fwd_results(x))
+for _op in (_op_bn_drop_skip_actx_fwd_raw, _op_bn_drop_skip_actx):
+    _op.register_fake(lambda x, skip, weight, bias, slope, eps, kind, param, mode, T, seed, offset:
+                      _fwd_results(x, skip, mode))
+_op_dropout_keyed.register_fake(lambda x, T, seed, offset: _new32(x, *x.shape))
+_op_bn_bwd_raw.register_fake(lambda dy, y, x, weight, mean, invstd, bias=None, relu_from_x=False: _bwd_results(dy, x))
+_op_bn_actx_bwd_raw.register_fake(lambda dy, x, weight, bias, slope, mean, invstd, kind, param, want_dslope=True:
+                                  _bwd_results(dy, x, kind, want_dslope))
+_op_bn_drop_actx_bwd_raw.register_fake(
+    lambda dy, x, weight, bias, slope, mean, invstd, kind, param, T, seed, offset, want_dslope=True:
+    _bwd_results(dy, x, kind, want_dslope))
+_op_bn_skip_actx_bwd_raw.register_fake(
+    lambda dy, x, skip, weight, bias, slope, mean, invstd, mode, kind, param, want_dskip=True, want_dslope=True:
+    _bwd_results(dy, x, kind, want_dslope, skip, want_dskip))
+_op_bn_drop_skip_actx_bwd_raw.register_fake(
+    lambda dy, x, skip, weight, bias, slope, mean, invstd, mode, kind, param, T, seed, offset, want_dskip=True,
+    want_dslope=True: _bwd_results(dy, x, kind, want_dslope, skip, want_dskip))
+_actx_autograd(_op_bn_actx, has_skip=False, has_drop=False)
+_actx_autograd(_op_bn_skip_actx, has_skip=True, has_drop=False)
+_actx_autograd(_op_bn_drop_actx, has_skip=False, has_drop=True)
+_actx_autograd(_op_bn_drop_skip_actx, has_skip=True, has_drop=True)
 
 
 # ---- softmax cross-entropy over the labelled rows (graphgym/loss.py:53-68, 20-37) -------------------------------
@@ -994,8 +743,7 @@ class BatchNorm1d(nn.BatchNorm1d):
     def forward(self, x):
         if x.dim() != 2:
             raise ValueError("expected [num_nodes, num_features]")
-        use_batch_stats = self.training or not self.track_running_stats
-        if not (use_batch_stats and x.is_cuda and x.size(0) > 1 and x.dtype != torch.bfloat16):   # bf16: torch
+        if not _batch_stats_on_engine(self, x):
             y = super().forward(x)
             return torch.relu(y) if self.relu else y
         y, mean, _, var_u = torch.ops.mp.bn_act(x, self.weight, self.bias, float(self.eps), bool(self.relu))
@@ -1006,12 +754,15 @@ class BatchNorm1d(nn.BatchNorm1d):
         return super().extra_repr() + f", relu={self.relu}"
 
 
-def _bn_on_engine(bn, x):
-    """BatchNorm1d.forward's rule for the fused passes: batch statistics, a device tensor of more than one row, not bf16,
-    and a BatchNorm that carries no fused ReLU of its own"""
-    return (isinstance(bn, nn.BatchNorm1d) and not getattr(bn, "relu", False)
-            and (bn.training or not bn.track_running_stats) and x.dim() == 2 and x.is_cuda and x.size(0) > 1
+def _batch_stats_on_engine(bn, x):
+    """the rule of every engine pass: batch statistics over a device tensor [N > 1, d] that is not bf16 (bf16: torch)"""
+    return ((bn.training or not bn.track_running_stats) and x.dim() == 2 and x.is_cuda and x.size(0) > 1
             and x.dtype != torch.bfloat16)
+
+
+def _bn_on_engine(bn, x):
+    """BatchNorm1d.forward's rule for the fused passes, and a BatchNorm that carries no fused ReLU of its own"""
+    return isinstance(bn, nn.BatchNorm1d) and not getattr(bn, "relu", False) and _batch_stats_on_engine(bn, x)
 
 
 class Dropout(nn.Dropout):

@@ -1,7 +1,8 @@
 """The skip stages without a device: argument validation of mp_bn_train_fwd_skip_f32 / mp_bn_train_bwd_skip_f32 on the C
 ABI (every refusal happens before a launch), schemas and fake kernels of mp::bn_skip_fwd_raw / bn_skip_bwd_raw /
-bn_skip_act, cfg.gnn.skip_every, the module tree of harness.GNN with stage_type skipsum / skipconcat against key lists
-written from graphgym/models/gnn.py:30-44, 84-102, and graphgym_plugin.accelerate() on a reference-style skip block."""
+bn_skip_act, the schemas of every other BatchNorm op and what the four *actx_bwd_raw ops return empty,
+cfg.gnn.skip_every, the module tree of harness.GNN with stage_type skipsum / skipconcat against key lists written
+from graphgym/models/gnn.py:30-44, 84-102, and graphgym_plugin.accelerate() on a reference-style skip block."""
 import ctypes as C
 import itertools
 
@@ -85,6 +86,35 @@ def test_backward_refuses_a_short_workspace(fake):
     assert _bwd(fake, out=None, ldo=0, dskip=None, lddskip=0, ws_bytes=0) == WORKSPACE
 
 
+_T4, _T5 = " -> (Tensor, Tensor, Tensor, Tensor)", " -> (Tensor, Tensor, Tensor, Tensor, Tensor)"
+_ACTX = "Tensor? weight, Tensor? bias, Tensor? slope, float eps, SymInt kind, float param"
+_ACTX_BWD = "Tensor? weight, Tensor? bias, Tensor? slope, Tensor mean, Tensor invstd"
+_KEY = "SymInt T, SymInt seed, SymInt offset"
+# the public signatures of the other BatchNorm ops and of dropout_keyed, without the "mp::<name>"
+_OTHER_SCHEMAS = {
+    "bn_fwd_raw": "(Tensor x, Tensor? weight, Tensor? bias, float eps, bool relu)" + _T4,
+    "bn_bwd_raw": "(Tensor dy, Tensor? y, Tensor x, Tensor? weight, Tensor mean, Tensor invstd, Tensor? bias=None, "
+                  "bool relu_from_x=False) -> (Tensor, Tensor, Tensor)",
+    "bn_act": "(Tensor x, Tensor? weight, Tensor? bias, float eps, bool relu)" + _T4,
+    "bn_actx_fwd_raw": f"(Tensor x, {_ACTX})" + _T4,
+    "bn_actx_bwd_raw": f"(Tensor dy, Tensor x, {_ACTX_BWD}, SymInt kind, float param, bool want_dslope=True)" + _T4,
+    "bn_actx": f"(Tensor x, {_ACTX})" + _T4,
+    "bn_skip_actx_fwd_raw": f"(Tensor x, Tensor skip, {_ACTX}, SymInt mode)" + _T4,
+    "bn_skip_actx_bwd_raw": f"(Tensor dy, Tensor x, Tensor skip, {_ACTX_BWD}, SymInt mode, SymInt kind, float param, "
+                            "bool want_dskip=True, bool want_dslope=True)" + _T5,
+    "bn_skip_actx": f"(Tensor x, Tensor skip, {_ACTX}, SymInt mode)" + _T4,
+    "bn_drop_actx_fwd_raw": f"(Tensor x, {_ACTX}, {_KEY})" + _T4,
+    "bn_drop_actx_bwd_raw": f"(Tensor dy, Tensor x, {_ACTX_BWD}, SymInt kind, float param, {_KEY}, "
+                            "bool want_dslope=True)" + _T4,
+    "bn_drop_actx": f"(Tensor x, {_ACTX}, {_KEY})" + _T4,
+    "bn_drop_skip_actx_fwd_raw": f"(Tensor x, Tensor skip, {_ACTX}, SymInt mode, {_KEY})" + _T4,
+    "bn_drop_skip_actx_bwd_raw": f"(Tensor dy, Tensor x, Tensor skip, {_ACTX_BWD}, SymInt mode, SymInt kind, "
+                                 f"float param, {_KEY}, bool want_dskip=True, bool want_dslope=True)" + _T5,
+    "bn_drop_skip_actx": f"(Tensor x, Tensor skip, {_ACTX}, SymInt mode, {_KEY})" + _T4,
+    "dropout_keyed": "(Tensor x, SymInt T, SymInt seed, SymInt offset) -> Tensor",
+}
+
+
 def test_schemas_and_fake_kernels():
     from torch._subclasses.fake_tensor import FakeTensorMode
     import graphgym_amd.nn as mpnn
@@ -99,7 +129,8 @@ def test_schemas_and_fake_kernels():
     assert str(ops.bn_skip_bwd_raw.default._schema) == (
         "mp::bn_skip_bwd_raw(Tensor dy, Tensor? out, Tensor x, Tensor? weight, Tensor mean, Tensor invstd, SymInt mode, "
         "bool want_dskip=True) -> (Tensor, Tensor, Tensor, Tensor)")
-    with FakeTensorMode():
+    fake_mode = FakeTensorMode()
+    with fake_mode:
         N, d, ds = 11, 8, 6
         x, w, b = torch.empty(N, d, device="cuda"), torch.empty(d, device="cuda"), torch.empty(d, device="cuda")
         for op in (ops.bn_skip_fwd_raw, ops.bn_skip_act):
@@ -116,6 +147,44 @@ def test_schemas_and_fake_kernels():
         dyc = torch.empty(N, ds + d, device="cuda")
         dx, dg, db, dskip = ops.bn_skip_bwd_raw(dyc, dyc, x, w, st, st, CONCAT)
         assert dx.shape == (N, d) and dskip.shape == (N, ds)
+    for name, schema in _OTHER_SCHEMAS.items():
+        assert str(getattr(ops, name).default._schema) == f"mp::{name}{schema}", name
+    # the four *actx_bwd_raw ops: dskip comes back EMPTY unless asked for AND there is an activation, dslope unless asked
+    # for AND the kind is PRELU; everything else has its shape whatever is asked
+    NONE, RELU, PRELU = mpnn.ACT_NONE, mpnn.ACT_RELU, mpnn.ACT_PRELU
+    key = (20000, 5, 7)
+    with fake_mode:
+        sl = torch.empty(1, device="cuda")
+        for fam, extra in (("bn_actx", ()), ("bn_drop_actx", key)):         # the forward fakes of the other families
+            for op in (getattr(ops, fam), getattr(ops, fam + "_fwd_raw")):
+                res = op(x, w, b, None, 1e-5, RELU, 0.0, *extra)
+                assert [tuple(t.shape) for t in res] == [(N, d), (d,), (d,), (d,)], fam
+                assert all(t.dtype == torch.float32 for t in res), fam
+        for fam, extra in (("bn_skip_actx", ()), ("bn_drop_skip_actx", key)):
+            for op, mode in itertools.product((getattr(ops, fam), getattr(ops, fam + "_fwd_raw")), (SUM, CONCAT)):
+                skip = torch.empty(N, d if mode == SUM else ds, device="cuda")
+                res = op(x, skip, w, b, sl, 1e-5, PRELU, 0.0, mode, *extra)
+                assert [tuple(t.shape) for t in res] == [(N, skip.size(1) + (d if mode == CONCAT else 0)), (d,), (d,), (d,)]
+        assert [tuple(t.shape) for t in ops.bn_bwd_raw(dy, None, x, w, st, st)] == [(N, d), (d,), (d,)]
+        for kind, want_dskip, want_dslope, mode in itertools.product((NONE, RELU, PRELU), (True, False), (True, False),
+                                                                     (SUM, CONCAT)):
+            s = sl if kind == PRELU else None
+            skip = torch.empty(N, d if mode == SUM else ds, device="cuda")
+            dyk = dy if mode == SUM else dyc
+            plain = [ops.bn_actx_bwd_raw(dy, x, w, b, s, st, st, kind, 0.0, want_dslope),
+                     ops.bn_drop_actx_bwd_raw(dy, x, w, b, s, st, st, kind, 0.0, *key, want_dslope)]
+            wants = (want_dskip, want_dslope)
+            skipped = [ops.bn_skip_actx_bwd_raw(dyk, x, skip, w, b, s, st, st, mode, kind, 0.0, *wants),
+                       ops.bn_drop_skip_actx_bwd_raw(dyk, x, skip, w, b, s, st, st, mode, kind, 0.0, *key, *wants)]
+            for res, n_results in [(r, 4) for r in plain] + [(r, 5) for r in skipped]:
+                what = (kind, want_dskip, want_dslope, mode, n_results)
+                assert len(res) == n_results, what
+                assert all(isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_cuda for t in res), what
+                dx, dg, db, dslope = res[0], res[1], res[2], res[-1]
+                assert dx.shape == (N, d) and dg.shape == db.shape == (d,), what
+                assert dslope.shape == ((1,) if (kind == PRELU and want_dslope) else (0,)), what
+            for res in skipped:
+                assert res[3].shape == (skip.shape if (want_dskip and kind != NONE) else (0,)), (kind, want_dskip, mode)
 
 
 def test_bn_skip_act_outside_the_kernels_domain_is_the_torch_composition():
