@@ -74,6 +74,10 @@ def test_opcheck(dev):
         (torch.ops.mp.spmm_edge_heads.default, (t(g.nnz, H), t(n, d), t(E, d), None, None, h, H, 1)),
         (torch.ops.mp.spmm_edge_heads.default, (t(g.nnz, H), t(n, d), t(E, d), t(n, d), t(d), h, H, 2)),
         (torch.ops.mp.spmm_edge_heads.default, (t(g.nnz, 1), t(n, d), t(E, d), t(n, d), None, h, 1, 0)),
+        # the other rungs of the head ladder under max (1 head) and with 3 heads (one launch per head, d = 24)
+        (torch.ops.mp.spmm_edge_heads.default, (t(g.nnz, 1), t(n, d), t(E, d), t(n, d), t(d), h, 1, 2)),
+        (torch.ops.mp.spmm_edge_heads.default, (t(g.nnz, 3), t(n, 24), t(E, 24), t(n, 24), t(24), h, 3, 1)),
+        (torch.ops.mp.spmm_edge_heads.default, (t(g.nnz, 3), t(n, 24), t(E, 24), None, None, h, 3, 2)),
         (torch.ops.mp.spmm_edge_heads_bwd_raw.default, (t(n, d, grad=False), w, x, m, tt, none, h, H, 1, 15)),
         (torch.ops.mp.spmm_edge_heads_bwd_raw.default, (t(n, d, grad=False), w, x, m, tt, win, h, H, 2, 15)),
         (torch.ops.mp.spmm_edge_heads_bwd_raw.default, (t(n, d, grad=False), w, x, m, None, none, h, H, 0, 5)),
