@@ -28,9 +28,11 @@
 //
 // What a wave gathers per stored entry is a policy of the two gather kernels (the entry sources below): XRows, the row
 // X[col], or EdgeRows, the rows X[col] and M[eid] of the two-gather form (fp32).  Both walk the entries through
-// MP_WALK_ENTRIES and share the launcher, the argument checks and the width choice.
+// MP_WALK_ENTRIES and share the launcher, the argument checks and the width choice.  SplineAggRows and SplineFoldRows
+// (mp_spline.h: two weights per entry; one gather into two sums, and its adjoint) are two more sources on the same walk.
 #include "common.h"
 #include "vecio.h"
+#include "../../include/mp_spline.h"
 #include <limits.h>
 #include <type_traits>
 
@@ -308,6 +310,100 @@ struct EdgeRows {
                                           RowAcc<F32, W, REDUCE, false>& acc) const {
     float v[W];
     edge_message<W, HAS_T>(xm.x, xm.m, ej >= 0, t, v);
+    acc.add(v, w, false, e);
+  }
+};
+
+// ---- one gather, two sums: messages weighted by an open degree-1 B-spline with two kernel matrices (layer.py:177-186) -
+// Every entry carries two weights w[e] = (w0, w1) of its own, in ENTRY order (mp_spline.h).  The two kernels are each
+// other's adjoint on the transposed pattern:
+//   SplineAggRows   P[r] = sum_e w0 X[col_e], Q[r] = sum_e w1 X[col_e]: one row load per entry, two running sums per row
+//                   (RowAcc::b, as the ID-GNN form keeps them).  The caller binds P and Q = P + d to the two halves of one
+//                   [N, 2d] row, so finish_row and the hub path store them as they store any P and Q.
+//   SplineFoldRows  Y[r] = sum_e (w0 Z[col_e, 0:d] + w1 Z[col_e, d:2d]): two row loads from one index, one sum.
+// The walk's own weight word is unused (WEIGHTED = false): a lane loads its entry's two weights beside its index word
+// and issue() broadcasts them with the index, so they travel in Rows to consume() as the index word does.  fp32, no marks.
+struct SplineArgs {
+  AggArgs<F32> a;
+  const float* w2;   // [nnz, 2]
+};
+
+template <int W>
+struct SplineAggRows {
+  using E = F32;
+  using Args = SplineArgs;
+  static constexpr int kW = W;
+  static constexpr bool kMarks = false;
+  struct Rows { float x[W]; float w0, w1; };
+  static __host__ __device__ __forceinline__ const AggArgs<F32>& agg(const Args& g) { return g.a; }
+
+  const Args& g;
+  const float* xlane;
+  int cv;
+  float w0v, w1v;
+
+  __device__ __forceinline__ SplineAggRows(const Args& g_, int c0ld) : g(g_), xlane(g_.a.X + c0ld) {}
+  __device__ __forceinline__ void start_row(int) {}
+  __device__ __forceinline__ void load_index(int me) {
+    cv = g.a.col[me];
+    w0v = g.w2[2 * (int64_t)me];
+    w1v = g.w2[2 * (int64_t)me + 1];
+  }
+  template <bool BRANCH2>
+  __device__ __forceinline__ void issue(int j, Rows& r, int& cj) const {
+    static_assert(BRANCH2, "the two sums are the two branches");
+    cj = bcast_i(cv, j);
+    r.w0 = bcast_f(w0v, j);
+    r.w1 = bcast_f(w1v, j);
+    load_vec<W>(xlane + (int64_t)cj * g.a.ldx, r.x);
+  }
+  template <int REDUCE>
+  __device__ __forceinline__ void consume(const Rows& r, int, float, int, RowAcc<F32, W, REDUCE, true>& acc) const {
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      acc.a[k] = fmaf(r.w0, r.x[k], acc.a[k]);
+      acc.b[k] = fmaf(r.w1, r.x[k], acc.b[k]);
+    }
+  }
+};
+
+template <int W>
+struct SplineFoldRows {
+  using E = F32;
+  using Args = SplineArgs;
+  static constexpr int kW = W;
+  static constexpr bool kMarks = false;
+  struct Rows { float a[W], b[W]; float w0, w1; };
+  static __host__ __device__ __forceinline__ const AggArgs<F32>& agg(const Args& g) { return g.a; }
+
+  const Args& g;
+  const float* alane;
+  const float* blane;
+  int cv;
+  float w0v, w1v;
+
+  __device__ __forceinline__ SplineFoldRows(const Args& g_, int c0ld)
+      : g(g_), alane(g_.a.X + c0ld), blane(g_.a.X + g_.a.d + c0ld) {}
+  __device__ __forceinline__ void start_row(int) {}
+  __device__ __forceinline__ void load_index(int me) {
+    cv = g.a.col[me];
+    w0v = g.w2[2 * (int64_t)me];
+    w1v = g.w2[2 * (int64_t)me + 1];
+  }
+  template <bool BRANCH2>
+  __device__ __forceinline__ void issue(int j, Rows& r, int& cj) const {
+    static_assert(!BRANCH2, "the fold has one sum");
+    cj = bcast_i(cv, j);
+    r.w0 = bcast_f(w0v, j);
+    r.w1 = bcast_f(w1v, j);
+    load_vec<W>(alane + (int64_t)cj * g.a.ldx, r.a);
+    load_vec<W>(blane + (int64_t)cj * g.a.ldx, r.b);
+  }
+  template <int REDUCE>
+  __device__ __forceinline__ void consume(const Rows& r, int, float w, int e, RowAcc<F32, W, REDUCE, false>& acc) const {
+    float v[W];
+#pragma unroll
+    for (int k = 0; k < W; ++k) v[k] = fmaf(r.w1, r.b[k], r.w0 * r.a[k]);
     acc.add(v, w, false, e);
   }
 };
@@ -873,6 +969,57 @@ static int agg_common(const int32_t* rowptr, const int32_t* col, const float* va
   }
 }
 
+// mp_spline_agg_f32 (FOLD false: X [n, d] -> the halves of Y [N, 2d]) and mp_spline_fold_f32 (FOLD true: X [n, 2d] ->
+// Y [N, d]): the checks of agg_common on their shapes, then the sum kernels on the two sources above.  The second half
+// of a row starts d elements behind the first: pick_width sees it as Q (agg) or through d % w == 0 on an aligned X (fold).
+template <bool FOLD>
+static int spline_common(const int32_t* rowptr, const int32_t* col, const float* w2, int64_t N, const int32_t* plan,
+                         const int32_t* counts, const float* X, int64_t ldx, float* Y, int64_t ldy, int32_t d, void* ws,
+                         size_t ws_bytes, hipStream_t st) {
+  if (!rowptr || !plan || !counts) return MP_ERR_INVALID_ARG;
+  if (N < 0 || d <= 0) return MP_ERR_INVALID_ARG;
+  if (d > INT32_MAX / 2) return MP_ERR_UNSUPPORTED;
+  if (ldx < (FOLD ? 2 : 1) * (int64_t)d || ldy < (FOLD ? 1 : 2) * (int64_t)d) return MP_ERR_INVALID_ARG;
+  if (N >= INT32_MAX) return MP_ERR_UNSUPPORTED;
+  if (N == 0) return MP_OK;
+  if (!X || !Y) return MP_ERR_INVALID_ARG;
+  const int32_t n_seg = counts[0], n_piece = counts[2];
+  if (n_seg < 1) return MP_ERR_INVALID_ARG;
+  if ((!col || !w2) && n_piece > 0) return MP_ERR_INVALID_ARG;   // (an operator without entries has neither)
+
+  size_t need = 0;
+  mp_spmm_ws_bytes(counts, d, MP_SUM, FOLD ? 0 : 1, &need);
+  if (need > 0 && (!ws || ws_bytes < need)) return MP_ERR_WORKSPACE;
+
+  SplineArgs g;
+  AggArgs<F32>& a = g.a;
+  g.w2 = w2;
+  a.rowptr = rowptr; a.col = col; a.val = nullptr;
+  a.header = plan;
+  a.seg_row = plan + PW_HEADER_WORDS;
+  a.n_seg = n_seg;
+  a.hub_deg = counts[6];
+  a.piece_edges = counts[7];
+  a.X = X; a.ldx = ldx; a.Y = Y; a.ldy = ldy;
+  a.Q = FOLD ? nullptr : Y + d; a.ldq = FOLD ? 0 : ldy;
+  a.S = nullptr; a.lds = 0; a.self_scale = 0.f; a.bias = nullptr; a.act = MP_ACT_NONE;
+  a.col_scale = nullptr; a.l2norm = 0; a.l2_eps = 1e-12f;
+  a.argmax = nullptr; a.d = d;
+  a.head_width = 0;
+  bind_hub(a, counts, MP_SUM, ws);
+
+  auto launch = [&](auto wc) {
+    constexpr int W = decltype(wc)::value;
+    if constexpr (FOLD) return launch_agg<SplineFoldRows<W>, MP_SUM, false, false>(g, counts, st);
+    else return launch_agg<SplineAggRows<W>, MP_SUM, false, true>(g, counts, st);
+  };
+  switch (pick_width(a, nullptr)) {
+    case 4: return launch(std::integral_constant<int, 4>());
+    case 2: return launch(std::integral_constant<int, 2>());
+    default: return launch(std::integral_constant<int, 1>());
+  }
+}
+
 template <class E>
 __global__ __launch_bounds__(kBlock) void max_bwd_kernel(const int32_t* __restrict__ col,
                                                          const float* __restrict__ val,
@@ -995,6 +1142,18 @@ int mp_idgnn_agg_f32(const int32_t* rowptr, const int32_t* col_marked, const flo
   if (N != 0 && !Q) return MP_ERR_INVALID_ARG;
   return agg_common<F32>(rowptr, col_marked, val, N, plan, counts_host, X, ldx, P, ldp, Q, ldq, d, MP_SUM,
                          nullptr, 0, 0.f, nullptr, MP_ACT_NONE, nullptr, ws, ws_bytes, as_stream(stream));
+}
+
+int mp_spline_agg_f32(const int32_t* rowptr, const int32_t* col, const float* w, int64_t N, const int32_t* plan,
+                      const int32_t* counts_host, const float* X, int64_t ldx, float* Y, int64_t ldy, int32_t d, void* ws,
+                      size_t ws_bytes, mp_stream_t stream) {
+  return spline_common<false>(rowptr, col, w, N, plan, counts_host, X, ldx, Y, ldy, d, ws, ws_bytes, as_stream(stream));
+}
+
+int mp_spline_fold_f32(const int32_t* rowptr, const int32_t* col, const float* w, int64_t N, const int32_t* plan,
+                       const int32_t* counts_host, const float* Z, int64_t ldz, float* Y, int64_t ldy, int32_t d, void* ws,
+                       size_t ws_bytes, mp_stream_t stream) {
+  return spline_common<true>(rowptr, col, w, N, plan, counts_host, Z, ldz, Y, ldy, d, ws, ws_bytes, as_stream(stream));
 }
 
 int mp_spmm_csr_heads_reduce_f32(const int32_t* rowptr, const int32_t* col, const float* a, int64_t N,

@@ -16,7 +16,9 @@ Importing this module is the whole integration:
   * the edge-feature attention keys 'generaledgeattconvv1', 'generaledgeattconvv2'
     (graphgym/contrib/layer/attconv.py:542-543), installed by install_edge_att() — a fourth dictionary, EDGE_ATT_KEYS,
   * the OGB keys 'generalogbconv' (graphgym/contrib/layer/generalconv_ogb.py:141) and 'sageinitconv'
-    (graphgym/contrib/layer/sageinitconv.py:115), installed by install_ogb() — a fifth dictionary, OGB_KEYS.
+    (graphgym/contrib/layer/sageinitconv.py:115), installed by install_ogb() — a fifth dictionary, OGB_KEYS,
+  * the built-in B-spline key 'splineconv' (graphgym/models/layer.py:177-186,232), installed by install_spline() — a
+    sixth dictionary, SPLINE_KEYS: with it every message-passing key of layer.py:224-235 is served.
 
 ``register_layer`` raises KeyError on a duplicate (register.py:6-10), and built-ins shadow
 registered keys (layer.py:238), so taking over an existing key is done by assignment into the
@@ -28,6 +30,7 @@ from . import edgeconv as EC
 from . import layers as L
 from . import ogbconv as OG
 from . import registry as R
+from . import splineconv as SP
 
 ID_KEYS = {
     'idconv': L.GeneralIDConv,
@@ -69,6 +72,9 @@ EDGE_ATT_KEYS = {
 OGB_KEYS = {
     'generalogbconv': OG.GeneralOGBConv,
     'sageinitconv': OG.SAGEinitConv,
+}
+SPLINE_KEYS = {
+    'splineconv': SP.SplineConv,
 }
 
 
@@ -126,11 +132,17 @@ def install_ogb(override=True):
     return _install_keys(OGB_KEYS, override)
 
 
+def install_spline(override=True):
+    """Register the B-spline key of SPLINE_KEYS with install()'s semantics; returns the keys taken."""
+    return _install_keys(SPLINE_KEYS, override)
+
+
 installed_keys = install(override=True)
 installed_design_keys = install_design(override=True)
 installed_edge_keys = install_edge(override=True)
 installed_edge_att_keys = install_edge_att(override=True)
 installed_ogb_keys = install_ogb(override=True)
+installed_spline_keys = install_spline(override=True)
 
 
 # ---- the post-ops of GraphGym's layer wrapper on the engine -------------------------------------------------

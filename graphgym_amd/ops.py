@@ -16,6 +16,7 @@ once under "what the registered operators share"; the per-head backward stands b
     edge_att_alpha / spmm_edge_heads   attention over messages with an edge feature (attconv.py:342-360)
     embed_sum(codes, table, offsets)   rows of stacked embedding tables summed per item (feature_encoder.py:74-81)
     spmm_code(g, x, table, codes, reduce)   aggregation of messages with a coded edge term (generalconv_ogb.py:115-118)
+    spline_agg / spline_fold(g, w, x)    one gather into two weighted sums, and its adjoint (SplineConv, layer.py:177-186)
 """
 import ctypes as C
 import os
@@ -2153,3 +2154,7 @@ _op_embed_sum.register_fake(lambda codes, table, offsets: table.new_empty((codes
 _op_embed_sum_bwd_raw.register_fake(lambda dy, codes, offsets, n_codes, disjoint: dy.new_empty((n_codes, dy.size(1))))
 _op_spmm_code.register_fake(lambda x, table, bias, qe, graph, reduce: _agg_results(x, graph, reduce == _lib.MAX))
 _op_spmm_code_bwd_raw.register_fake(lambda dy, argmax, qe, graph, reduce, n_codes: dy.new_empty((n_codes, dy.size(1))))
+
+
+# ---- one gather, two sums: the B-spline layer's aggregation and its adjoint (spline_ops.py, over the helpers above) ----
+from .spline_ops import _raw_spline, spline_agg, spline_fold   # noqa: E402,F401
