@@ -6,6 +6,10 @@ not bundled).  Task: a synthetic one — the balanced degree class of a node (gr
 degrees on the device) from a noisy copy of its log-degree.  Validation runs on the whole graph (val.sampler: full_batch).
 
     python examples/train_sampled_ba.py --nodes 200000 --epochs 5 --sampler saint_rw
+    python examples/train_sampled_ba.py --nodes 200000 --epochs 5 --sampler neighbor_subgraph --batch-size 1024
+
+neighbor_subgraph (graphgym_amd/neighbor.py) trains on the sampled tree of --batch-size seed nodes under the fanouts
+cfg.train.neighbor_sizes[:3] = [20, 15, 10], with the loss on the seeds; an epoch visits every training node once.
 """
 import argparse
 import json
@@ -23,15 +27,17 @@ from graphgym_amd import graphgen, harness as H, samplers, structure  # noqa: E4
 from graphgym_amd.config import cfg  # noqa: E402
 
 
-def main():
+def main(argv=None):
+    """one JSON line per epoch; returns the records"""
     ap = argparse.ArgumentParser()
     ap.add_argument("--nodes", type=int, default=200000)
     ap.add_argument("--epochs", type=int, default=5)
-    ap.add_argument("--sampler", default="saint_rw", choices=samplers.KINDS + ("full_batch",))
-    ap.add_argument("--batch-size", type=int, default=2000, help="roots / draws per batch (saint_*)")
+    ap.add_argument("--sampler", default="saint_rw", choices=samplers.KINDS + ("full_batch", "neighbor_subgraph"))
+    ap.add_argument("--batch-size", type=int, default=2000,
+                    help="roots / draws per batch (saint_*), seeds per batch (neighbor_subgraph)")
     ap.add_argument("--parts", type=int, default=16, help="train.train_parts (random_node)")
     ap.add_argument("--seed", type=int, default=0)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     n, classes = args.nodes, 10
 
@@ -56,6 +62,7 @@ def main():
     opt = torch.optim.Adam(model.parameters(), lr=cfg.optim.base_lr)
     train = samplers.loader_from_cfg(cfg, base, x, y, train_mask, "train", seed=args.seed)
     val = samplers.loader_from_cfg(cfg, base, x, y, ~train_mask, "val")
+    records = []
     for epoch in range(args.epochs):
         model.train()
         torch.cuda.synchronize()
@@ -71,10 +78,11 @@ def main():
         model.eval()
         with torch.no_grad():
             pred, true = model(next(iter(val)))
-        print(json.dumps({"epoch": epoch, "sampler": args.sampler, "batches": len(train),
-                          "nodes_per_batch": nodes // len(train), "train_loss": float(torch.stack(losses).mean()),
-                          "val_acc": float((pred.argmax(1) == true).float().mean()), "seconds": round(seconds, 3)}),
-              flush=True)
+        records.append({"epoch": epoch, "sampler": args.sampler, "batches": len(train),
+                        "nodes_per_batch": nodes // len(train), "train_loss": float(torch.stack(losses).mean()),
+                        "val_acc": float((pred.argmax(1) == true).float().mean()), "seconds": round(seconds, 3)})
+        print(json.dumps(records[-1]), flush=True)
+    return records
 
 
 if __name__ == "__main__":

@@ -1,5 +1,5 @@
 // Integer helpers shared by the keyed samplers (link.hip: negative sampling; sample.hip: mini-batch subgraph samplers;
-// centrality.hip: one-hot ids) and the keyed dropout mask (bn_drop.hip).
+// neighbor.hip: the neighbour sampler; centrality.hip: one-hot ids) and the keyed dropout mask (bn_drop.hip).
 // Integer mixing only: a draw is a pure function of its key, never of the launch geometry.
 #pragma once
 #include "common.h"
@@ -49,7 +49,7 @@ __device__ __forceinline__ void drop_keep(const DropKey& k, int64_t r, int c0, b
   }
 }
 
-// ---- the keyed bijection (link.hip: ranks of non-edges; centrality.hip: one-hot ids) -------------------------------------
+// ---- the keyed bijection (link.hip: ranks of non-edges; centrality.hip: one-hot ids; neighbor.hip: row positions) ---------
 // perm(i) on [0, C): a balanced Feistel network on 2b bits, b = max(1, ceil(bits(C - 1) / 2)), walked until the value is
 // below C (cycle walking: the domain is below 4 C, fewer than 4 encryptions on average, and the walk from a start below
 // C always returns below C because the network is a bijection).  The round keys come from (seed, offset, g).  The caller
@@ -63,13 +63,17 @@ __device__ __forceinline__ uint32_t feistel_round(uint32_t half, uint32_t key) {
   return x ^ (x >> 16);
 }
 
-__device__ __forceinline__ uint64_t keyed_perm(uint64_t seed, uint64_t offset, uint64_t g, uint64_t i, int64_t C) {
+// the round keys of (seed, offset, g): a caller that permutes several i under one g (neighbor.hip: the positions of one
+// row) computes them once
+__device__ __forceinline__ void perm_keys(uint64_t seed, uint64_t offset, uint64_t g, uint32_t (&key)[kFeistelRounds]) {
   uint64_t h = mix64(seed + kGolden);
   h = mix64((h ^ offset) + kGolden);
   h = mix64((h ^ g) + kGolden);
-  uint32_t key[kFeistelRounds];
 #pragma unroll
   for (int k = 0; k < kFeistelRounds; ++k) key[k] = (uint32_t)(mix64(h + (uint64_t)(k + 1) * kGolden) >> 32);
+}
+
+__device__ __forceinline__ uint64_t perm_walk(const uint32_t (&key)[kFeistelRounds], uint64_t i, int64_t C) {
   const int bits = C > 1 ? 64 - __builtin_clzll((uint64_t)(C - 1)) : 0;
   const int b = bits > 1 ? (bits + 1) >> 1 : 1;
   const uint32_t mask = b >= 32 ? 0xFFFFFFFFu : ((1u << b) - 1u);
@@ -85,6 +89,12 @@ __device__ __forceinline__ uint64_t keyed_perm(uint64_t seed, uint64_t offset, u
     x = ((uint64_t)L << b) | R;
   } while (x >= (uint64_t)C);
   return x;
+}
+
+__device__ __forceinline__ uint64_t keyed_perm(uint64_t seed, uint64_t offset, uint64_t g, uint64_t i, int64_t C) {
+  uint32_t key[kFeistelRounds];
+  perm_keys(seed, offset, g, key);
+  return perm_walk(key, i, C);
 }
 
 // first index in [lo, hi) whose value is above key

@@ -430,8 +430,10 @@ def loader_from_cfg(cfg, base, x, y, label_index_mask, split="train", seed=0):
     """The loader of graphgym/loader_pyg.py:204-255 for one graph: cfg.train.sampler for split 'train', cfg.val.sampler
     for every other split.  full_batch: the whole graph; random_node (cfg.train.train_parts — no default: ValueError
     without it), saint_node / saint_edge / saint_rw (cfg.train.batch_size, walk_length, iter_per_epoch): a
-    SubgraphLoader.  neighbor and cluster raise NotImplementedError with the reason; any other name raises the
-    reference's NotImplementedError."""
+    SubgraphLoader.  neighbor_subgraph (the project's own name, graphgym_amd/neighbor.py): a NeighborLoader over the
+    split's nodes with the fanouts cfg.train.neighbor_sizes[:cfg.gnn.layers_mp] and cfg.train.batch_size seeds a batch.
+    neighbor (PyG's per-layer bipartite blocks) and cluster raise NotImplementedError with the reason; any other name
+    raises the reference's NotImplementedError."""
     tr = cfg.train
     sampler = tr.sampler if split == "train" else cfg.val.sampler
     if sampler == "full_batch":
@@ -442,6 +444,10 @@ def loader_from_cfg(cfg, base, x, y, label_index_mask, split="train", seed=0):
                                   "consume either")
     if sampler == "cluster":
         raise NotImplementedError("cluster sampler is not implemented: ClusterLoader needs a METIS partition of the base")
+    if sampler == "neighbor_subgraph":
+        from .neighbor import NeighborLoader, plan_neighbor
+        sizes = list(tr.neighbor_sizes)[:cfg.gnn.layers_mp]
+        return NeighborLoader(base, x, y, label_index_mask, plan_neighbor(base, sizes, tr.batch_size), seed)
     if sampler not in KINDS:
         raise NotImplementedError("%s sampler is not implemented!" % sampler)
     if sampler == "random_node":
