@@ -270,6 +270,8 @@ class CSRGraph:
         g._row_ids = getattr(self, "_row_ids", None)
         g._pattern_of = self if getattr(self, "_pattern_of", None) is None else self._pattern_of
         g._ego_ids = getattr(self, "_ego_ids", None)
+        if "_max_row" in self.__dict__:           # the longest row is the pattern's: no second reduction and host read
+            g.__dict__["_max_row"] = self.__dict__["_max_row"]
         return g
 
     @property

@@ -16,6 +16,7 @@ model shapes of the reference's two entry points and its training step order.
     tfg_loss       mean softmax-CE over node_label_index + 5e-4 * sum ||kernel||^2 / 2
                    (graphgym/loss.py:53-68)
 """
+import os
 import types
 
 import torch
@@ -397,6 +398,34 @@ class GNNGraphHead(nn.Module):
         return batch.graph_feature, batch.graph_label
 
 
+# GNNEdgeHead sends its pairs to the engine's pair decoders (graphgym_amd/pair_ops.py: no [2, K, d] gather in either
+# direction) when the node features are fp32 on the device, K * d >= PAIR_DECODE_MIN and MP_PAIR_DECODE is not "0";
+# everything else (CPU tensors, bf16, small batches, PAIR_DECODE_MIN = None) is the reference's composition, unchanged.
+# The value is MEASURED: the smallest power of two at which the engine route, forward + backward with the index build
+# included, is no slower than the composition at d = 64 and at d = 256 (scripts/pair_decode_ab.py on link_batch of
+# BA(1e6, 5), profiles/pair_decode_ab.jsonl): dot and cosine_similarity lose up to K d = 2^24
+# (cosine at d = 256: 3.62 against 3.27 ms) and win from 2^25 on (1.2 x at d = 256, 1.8 - 2.5 x at d = 64).  The concat
+# decoding crosses sixteen times later — its two products over the N nodes and its three index builds cost 8 - 9 ms
+# whatever K is: it loses at 2^28 at d = 256 (9.19 against 7.78 ms) and wins from 2^29 on — so it takes the route from
+# PAIR_DECODE_MIN * PAIR_DECODE_CONCAT on; one number for all three would either send concat batches to a slower route or
+# keep score batches that run 2 - 5 x faster off it.
+# The floor is a condition, not a measurement: the threshold exceeds K * d of every test that ran a GNNEdgeHead before
+# the route existed, so that those keep seeing the composition — the largest is PAIR_DECODE_FLOOR = 1514 pairs x 32 (the
+# train batch of tests/test_link_pred_gpu.py::test_edge_head_without_the_transform; test_eval_gpu.py reaches 1388 x 32,
+# test_edge_nets_gpu.py 30 x 16, test_poison_gpu.py runs no head).
+PAIR_DECODE_MIN = 1 << 25
+PAIR_DECODE_CONCAT = 16
+PAIR_DECODE_FLOOR = 48448
+
+
+def pair_decode_route(on_device, dtype, K, d, concat=False):
+    """the route rule of GNNEdgeHead on the facts it depends on: True -> the engine's pair decoders"""
+    if PAIR_DECODE_MIN is None or os.environ.get("MP_PAIR_DECODE", "1") == "0":
+        return False
+    least = PAIR_DECODE_MIN * (PAIR_DECODE_CONCAT if concat else 1)
+    return bool(on_device and dtype == torch.float32 and K * d >= least)
+
+
 class GNNEdgeHead(nn.Module):
     """graphgym/models/head.py:40-85: decode the label pairs batch.edge_label_index [2, K] from the node embeddings.
     cfg.model.edge_decoding 'concat': MLP(2 dim_in, dim_out) on cat(h[a], h[b]); 'dot' / 'cosine_similarity': MLP(dim_in,
@@ -419,9 +448,52 @@ class GNNEdgeHead(nn.Module):
     def _apply_index(self, batch):
         return batch.node_feature[batch.edge_label_index], batch.edge_label
 
+    def _pair_route(self, h, index):
+        """whether the pairs go to graphgym_amd.pair_ops (pair_decode_route, above the class)"""
+        if not (isinstance(h, torch.Tensor) and isinstance(index, torch.Tensor) and h.dim() == 2
+                and index.dim() == 2 and index.size(0) == 2 and index.dtype == torch.int64
+                and (index.size(1) <= 1 or index.stride(1) == 1)):
+            return False
+        return pair_decode_route(h.is_cuda and index.is_cuda, h.dtype, index.size(1), h.size(1),
+                                 concat=self.decoding == 'concat')
+
+    def _concat_pairs(self, batch, pair_index):
+        """the concat decoding without cat((h[a], h[b]), -1): the first nn.Linear of layer_post_mp, weight [m, 2d],
+        distributes over the halves, cat(h[a], h[b]) W^T = (h W[:, :d]^T)[a] + (h W[:, d:]^T)[b] — two products over the N
+        nodes instead of one over the K pairs, then ops.pair_sum; whatever follows that Linear in the MLP (BatchNorm,
+        activation and the later layers for layers_post_mp > 1) runs on the [K, m] rows as it is.  The state dict is
+        unchanged: the column halves of the weight are views."""
+        from . import ops
+        h = batch.node_feature
+        d = h.size(1)
+        first, *rest = list(self.layer_post_mp.model)
+        inner = list(first.children()) if isinstance(first, GeneralMultiLayer) else []
+        lin = (inner[0].layer if inner else first).model
+        W = lin.weight
+        # the two half products take the dispatch of the module's own forward (graphgym_amd.nn.linear: the narrow-output
+        # weight gradient, the engine's transform on wide outputs); the bias joins in pair_sum
+        z = ops.pair_sum(mpnn.linear(h, W[:, :d]), mpnn.linear(h, W[:, d:]), batch.edge_label_index, lin.bias,
+                         pair_index=pair_index)
+        if inner:
+            z = inner[0]._post(z)
+            if inner[0].has_l2norm:
+                z = F.normalize(z, p=2, dim=1)
+            for layer in inner[1:]:
+                z = layer(z)
+        for layer in rest:
+            z = layer(z)
+        return z
+
     def forward(self, batch):
         if self.decoding != 'concat':
             batch = self.layer_post_mp(batch)
+        if self._pair_route(batch.node_feature, batch.edge_label_index):
+            from . import ops
+            pi = getattr(batch, "pair_index", None)     # a PairIndex built ahead; used when its stamp matches
+            if self.decoding == 'concat':
+                return self._concat_pairs(batch, pi), batch.edge_label
+            return ops.pair_score(batch.node_feature, batch.edge_label_index, cosine=self.decoding != 'dot',
+                                  pair_index=pi), batch.edge_label
         pred, label = self._apply_index(batch)
         a, b = pred[0], pred[1]
         if self.decoding == 'concat':

@@ -910,6 +910,25 @@ class _NarrowHead(torch.autograd.Function):
         return dx, (None if dW is None else dW.t()), db
 
 
+def linear(x, weight, bias=None, relu=False):
+    """act(x W^T + b) by Linear's dispatch, on any weight [out, in] — a parameter or a view of one (the column halves of
+    the edge head's first layer, harness.GNNEdgeHead._concat_pairs)"""
+    from . import ops
+    out_features, in_features = weight.shape
+    # the engine's kernels pay off on wide outputs over many rows (scripts/linear_bench.py: forward + backward
+    # 39.8 vs 45.0 ms at 10^7 x 256 -> 256, 18.6 vs 27.8 ms at 1 -> 256; the library wins at 256 -> 10 and on
+    # small batches), so narrow heads and small inputs stay on the library
+    if (x.dim() == 2 and x.is_cuda and x.dtype == torch.float32 and out_features <= 16 and not relu
+            and in_features % 4 == 0 and x.size(0) >= (1 << 17) and x.stride(1) == 1 and x.stride(0) % 4 == 0
+            and x.data_ptr() % 16 == 0 and torch.is_grad_enabled()):
+        return _NarrowHead.apply(x, weight, bias)
+    if (x.dim() != 2 or not x.is_cuda or x.dtype != torch.float32 or out_features < 32
+            or x.size(0) * out_features < (1 << 23)):
+        y = F.linear(x, weight, bias)
+        return torch.relu(y) if relu else y
+    return ops.dense_fused(x, weight.t(), bias=bias, relu=relu)
+
+
 class Linear(nn.Linear):
     """torch.nn.Linear (same parameters, same state dict) whose forward is the engine's transform kernel with bias
     and an optional ReLU fused into the store — the keras Dense(d, relu) / Dense(d) of the TF path's MLPs
@@ -922,19 +941,7 @@ class Linear(nn.Linear):
         self.relu = bool(relu)
 
     def forward(self, x):
-        from . import ops
-        # the engine's kernels pay off on wide outputs over many rows (scripts/linear_bench.py: forward + backward
-        # 39.8 vs 45.0 ms at 10^7 x 256 -> 256, 18.6 vs 27.8 ms at 1 -> 256; the library wins at 256 -> 10 and on
-        # small batches), so narrow heads and small inputs stay on the library
-        if (x.dim() == 2 and x.is_cuda and x.dtype == torch.float32 and self.out_features <= 16 and not self.relu
-                and self.in_features % 4 == 0 and x.size(0) >= (1 << 17) and x.stride(1) == 1 and x.stride(0) % 4 == 0
-                and x.data_ptr() % 16 == 0 and torch.is_grad_enabled()):
-            return _NarrowHead.apply(x, self.weight, self.bias)
-        if (x.dim() != 2 or not x.is_cuda or x.dtype != torch.float32 or self.out_features < 32
-                or x.size(0) * self.out_features < (1 << 23)):
-            y = F.linear(x, self.weight, self.bias)
-            return torch.relu(y) if self.relu else y
-        return ops.dense_fused(x, self.weight.t(), bias=self.bias, relu=self.relu)
+        return linear(x, self.weight, self.bias, self.relu)
 
     def extra_repr(self):
         return super().extra_repr() + (", relu=True" if self.relu else "")

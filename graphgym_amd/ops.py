@@ -17,6 +17,7 @@ once under "what the registered operators share"; the per-head backward stands b
     embed_sum(codes, table, offsets)   rows of stacked embedding tables summed per item (feature_encoder.py:74-81)
     spmm_code(g, x, table, codes, reduce)   aggregation of messages with a coded edge term (generalconv_ogb.py:115-118)
     spline_agg / spline_fold(g, w, x)    one gather into two weighted sums, and its adjoint (SplineConv, layer.py:177-186)
+    pair_score / pair_sum(.., index)     the link-prediction head's pair decodings without a [K, d] tensor (head.py:62-85)
 """
 import ctypes as C
 import os
@@ -2158,3 +2159,7 @@ _op_spmm_code_bwd_raw.register_fake(lambda dy, argmax, qe, graph, reduce, n_code
 
 # ---- one gather, two sums: the B-spline layer's aggregation and its adjoint (spline_ops.py, over the helpers above) ----
 from .spline_ops import _raw_spline, spline_agg, spline_fold   # noqa: E402,F401
+
+
+# ---- the pair decoders of the link-prediction head (pair_ops.py, over the helpers above) ------------------------------
+from .pair_ops import PairIndex, pair_index, pair_score, pair_sum   # noqa: E402,F401
