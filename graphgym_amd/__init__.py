@@ -8,6 +8,7 @@ from . import hostcpu
 from ._lib import EngineError, LIB_PATH, lib  # noqa: F401
 from .graph import CSRGraph  # noqa: F401
 from . import ops  # noqa: F401
+from . import maxbwd_ops  # noqa: F401  (torch.ops.mp.spmm_max_bwd_pull_raw / spmm_heads_max_bwd_pull_raw)
 from . import link_pred  # noqa: F401
 from . import samplers  # noqa: F401
 from . import graph_loader  # noqa: F401

@@ -19,7 +19,8 @@ SOURCES = ["spmm.hip", "fused.hip", "fused_hot.hip", "csr_build.hip", "attn.hip"
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "vecio.h"), os.path.join(CSRC, "bf16x3.h"), os.path.join(CSRC, "fused_pc.h"), os.path.join(CSRC, "draws.h"), os.path.join(CSRC, "act.h"), os.path.join(CSRC, "bn_kernels.h"),
            os.path.join(ROOT, "include", "mp_engine.h"), os.path.join(ROOT, "include", "mp_eval.h"),
            os.path.join(ROOT, "include", "mp_structure.h"), os.path.join(ROOT, "include", "mp_spline.h"),
-           os.path.join(ROOT, "include", "mp_neighbor.h"), os.path.join(ROOT, "include", "mp_pair.h")]
+           os.path.join(ROOT, "include", "mp_neighbor.h"), os.path.join(ROOT, "include", "mp_pair.h"),
+           os.path.join(ROOT, "include", "mp_maxbwd.h")]
 ARCH = "gfx950"
 # per-source flags.  fused_hot.hip (the hot kernels of fused_pc.h alone): uniform branches stay branches, not structurized
 # into two one-sided regions — the gather's per-row choice of cache policy otherwise leaves control-flow paths with zero

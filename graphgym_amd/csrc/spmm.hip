@@ -29,10 +29,12 @@
 // What a wave gathers per stored entry is a policy of the two gather kernels (the entry sources below): XRows, the row
 // X[col], or EdgeRows, the rows X[col] and M[eid] of the two-gather form (fp32).  Both walk the entries through
 // MP_WALK_ENTRIES and share the launcher, the argument checks and the width choice.  SplineAggRows and SplineFoldRows
-// (mp_spline.h: two weights per entry; one gather into two sums, and its adjoint) are two more sources on the same walk.
+// (mp_spline.h: two weights per entry; one gather into two sums, and its adjoint) are two more sources on the same walk,
+// MaxBwdRows (the backward of max as a gather over the transposed pattern: ops.deterministic()) a fifth.
 #include "common.h"
 #include "vecio.h"
 #include "../../include/mp_spline.h"
+#include "../../include/mp_maxbwd.h"
 #include <limits.h>
 #include <type_traits>
 
@@ -405,6 +407,61 @@ struct SplineFoldRows {
 #pragma unroll
     for (int k = 0; k < W; ++k) v[k] = fmaf(r.w1, r.b[k], r.w0 * r.a[k]);
     acc.add(v, w, false, e);
+  }
+};
+
+// ---- two gathers, one masked sum: the backward of max in pull form ---------------------------------
+// The walk runs over the TRANSPOSED pattern: a row is a source j, an entry t of it is one forward entry e = pos[t] of
+// destination i = col[t], and
+//   dX[j, c] = sum over row j's entries t, in their stored order, of [argmax[i_t, c] == pos_t] * w_t * dY[i_t, c]
+// with w the forward weights permuted into the transposed order (the walk's own weight word: val [nnz], or [nnz, NH]
+// for the heads form).  A lane loads its entry's (col, pos) pair; issue() broadcasts the pair and issues the row loads
+// of argmax[i] (int32) and dY[i]; consume() turns the match mask into the message.  Both loads are issued for every
+// entry, whatever the argmax row says: the dY load would otherwise depend on the argmax load's return (two round trips
+// in a row per entry), and a per-lane predicate on it saves no traffic at all — a 128-byte line of dY is fetched when
+// any of its 32 columns matched.  An empty destination row has argmax = -1, which equals no pos: no branch.  E = Bf16
+// reads a bf16 dY, sums in fp32 and stores a bf16 dX rounded once.  No marks, no second branch, sum only.
+template <class E>
+struct MaxBwdArgs {
+  AggArgs<E> a;              // the transposed pattern; X = dY (rows by destination), Y = dX (rows by source)
+  const int32_t* pos;        // [nnz] forward entry of every transposed entry
+  const int32_t* argmax;     // [N_dst, >= d] winning forward entry per destination and column, -1: none
+  int64_t lda;
+};
+
+template <class E_, int W>
+struct MaxBwdRows {
+  using E = E_;
+  using Args = MaxBwdArgs<E>;
+  static constexpr int kW = W;
+  static constexpr bool kMarks = false;
+  struct Rows { typename E::template Raw<W> g; int am[W]; };
+  static __host__ __device__ __forceinline__ const AggArgs<E>& agg(const Args& g) { return g.a; }
+
+  const Args& g;
+  const typename E::T* glane;
+  const int32_t* alane;
+  int cv, pv;
+
+  __device__ __forceinline__ MaxBwdRows(const Args& g_, int c0ld)
+      : g(g_), glane(g_.a.X + c0ld), alane(g_.argmax + c0ld) {}
+  __device__ __forceinline__ void start_row(int) {}
+  __device__ __forceinline__ void load_index(int me) { cv = g.a.col[me]; pv = g.pos[me]; }
+  template <bool BRANCH2>
+  __device__ __forceinline__ void issue(int j, Rows& r, int& pj) const {
+    static_assert(!BRANCH2, "the pull form has one sum");
+    const int i = bcast_i(cv, j);
+    pj = bcast_i(pv, j);
+    E::template load_raw<W>(glane + (int64_t)i * g.a.ldx, r.g);
+    load_i32<W>(alane + (int64_t)i * g.lda, r.am);
+  }
+  template <int REDUCE>
+  __device__ __forceinline__ void consume(const Rows& r, int pj, float w, int, RowAcc<E, W, REDUCE, false>& acc) const {
+    static_assert(REDUCE == MP_SUM, "the pull form is a sum");
+    float v[W];
+    E::template widen<W>(r.g, v);
+#pragma unroll
+    for (int k = 0; k < W; ++k) acc.a[k] = fmaf(w, r.am[k] == pj ? v[k] : 0.f, acc.a[k]);
   }
 };
 
@@ -1020,6 +1077,67 @@ static int spline_common(const int32_t* rowptr, const int32_t* col, const float*
   }
 }
 
+// mp_spmm_max_bwd_pull_f32 / _bf16 / mp_spmm_heads_max_bwd_pull_f32: the checks of agg_common on the transposed
+// operator, then the sum kernels on MaxBwdRows.  heads <= 1: w [nnz] or NULL (ones); 2 / 4 / 8 (fp32): w [nnz, heads].
+template <class E>
+static int max_bwd_pull_common(const int32_t* t_rowptr, const int32_t* t_col, const int32_t* t_pos, const float* w,
+                               int64_t n_src, int64_t nnz, const int32_t* plan, const int32_t* counts, int32_t heads,
+                               const int32_t* argmax, int64_t lda, const typename E::T* dY, int64_t ldy, int32_t d,
+                               typename E::T* dX, int64_t ldx, void* ws, size_t ws_bytes, hipStream_t st) {
+  if (!t_rowptr || !plan || !counts) return MP_ERR_INVALID_ARG;
+  if (n_src < 0 || nnz < 0 || d <= 0 || lda < d || ldy < d || ldx < d) return MP_ERR_INVALID_ARG;
+  if (heads < 1 || d % heads || (heads > 1 && !w)) return MP_ERR_INVALID_ARG;
+  if (n_src >= INT32_MAX || nnz >= INT32_MAX) return MP_ERR_UNSUPPORTED;
+  if (heads > 1 && (!E::kExtras || (heads != 2 && heads != 4 && heads != 8))) return MP_ERR_UNSUPPORTED;
+  if (n_src == 0) return MP_OK;
+  if (!dX) return MP_ERR_INVALID_ARG;
+  if (nnz > 0 && (!t_col || !t_pos || !argmax || !dY)) return MP_ERR_INVALID_ARG;   // (without entries nothing reads them)
+  const int32_t n_seg = counts[0];
+  if (n_seg < 1) return MP_ERR_INVALID_ARG;
+
+  size_t need = 0;
+  mp_spmm_ws_bytes(counts, d, MP_SUM, 0, &need);
+  if (need > 0 && (!ws || ws_bytes < need)) return MP_ERR_WORKSPACE;
+
+  MaxBwdArgs<E> g;
+  AggArgs<E>& a = g.a;
+  g.pos = t_pos; g.argmax = argmax; g.lda = lda;
+  a.rowptr = t_rowptr; a.col = t_col; a.val = w;
+  a.header = plan;
+  a.seg_row = plan + PW_HEADER_WORDS;
+  a.n_seg = n_seg;
+  a.hub_deg = counts[6];
+  a.piece_edges = counts[7];
+  a.X = dY; a.ldx = ldy; a.Y = dX; a.ldy = ldx; a.Q = nullptr; a.ldq = 0;
+  a.S = nullptr; a.lds = 0; a.self_scale = 0.f; a.bias = nullptr; a.act = MP_ACT_NONE;
+  a.col_scale = nullptr; a.l2norm = 0; a.l2_eps = 1e-12f;
+  a.argmax = nullptr; a.d = d;
+  a.head_width = heads > 1 ? d / heads : 0;
+  bind_hub(a, counts, MP_SUM, ws);
+
+  auto launch = [&](auto wc) {
+    using S = MaxBwdRows<E, decltype(wc)::value>;
+    if constexpr (E::kExtras) {
+      switch (heads) {
+        case 2: return launch_agg<S, MP_SUM, true, false, 2>(g, counts, st);
+        case 4: return launch_agg<S, MP_SUM, true, false, 4>(g, counts, st);
+        case 8: return launch_agg<S, MP_SUM, true, false, 8>(g, counts, st);
+      }
+    }
+    return w ? launch_agg<S, MP_SUM, true, false>(g, counts, st) : launch_agg<S, MP_SUM, false, false>(g, counts, st);
+  };
+  int wd = pick_width(a, nullptr);
+  while (wd > 1 && (lda % wd || !aligned(argmax, 4u * (wd < 4 ? wd : 4)))) wd >>= 1;   // the argmax row: int32 vectors of <= 4
+  if constexpr (E::kMaxW == 8) {
+    if (wd == 8) return launch(std::integral_constant<int, 8>());
+  }
+  switch (wd) {
+    case 4: return launch(std::integral_constant<int, 4>());
+    case 2: return launch(std::integral_constant<int, 2>());
+    default: return launch(std::integral_constant<int, 1>());
+  }
+}
+
 template <class E>
 __global__ __launch_bounds__(kBlock) void max_bwd_kernel(const int32_t* __restrict__ col,
                                                          const float* __restrict__ val,
@@ -1289,6 +1407,32 @@ int mp_spmm_max_bwd_bf16(const int32_t* col, const float* val, const int32_t* ar
                      val, argmax, (const uint16_t*)dY, ldy, N, d, dX, ldx);
   MP_LAUNCH_CHECK();
   return MP_OK;
+}
+
+int mp_spmm_max_bwd_pull_f32(const int32_t* t_rowptr, const int32_t* t_col, const int32_t* t_pos, const float* t_val,
+                             int64_t n_src, int64_t nnz, const int32_t* plan, const int32_t* counts_host,
+                             const int32_t* argmax, int64_t lda, const float* dY, int64_t ldy, int32_t d, float* dX,
+                             int64_t ldx, void* ws, size_t ws_bytes, mp_stream_t stream) {
+  return max_bwd_pull_common<F32>(t_rowptr, t_col, t_pos, t_val, n_src, nnz, plan, counts_host, 1, argmax, lda, dY, ldy,
+                                  d, dX, ldx, ws, ws_bytes, as_stream(stream));
+}
+
+int mp_spmm_max_bwd_pull_bf16(const int32_t* t_rowptr, const int32_t* t_col, const int32_t* t_pos, const float* t_val,
+                              int64_t n_src, int64_t nnz, const int32_t* plan, const int32_t* counts_host,
+                              const int32_t* argmax, int64_t lda, const void* dY, int64_t ldy, int32_t d, void* dX,
+                              int64_t ldx, void* ws, size_t ws_bytes, mp_stream_t stream) {
+  return max_bwd_pull_common<Bf16>(t_rowptr, t_col, t_pos, t_val, n_src, nnz, plan, counts_host, 1, argmax, lda,
+                                   (const uint16_t*)dY, ldy, d, (uint16_t*)dX, ldx, ws, ws_bytes, as_stream(stream));
+}
+
+int mp_spmm_heads_max_bwd_pull_f32(const int32_t* t_rowptr, const int32_t* t_col, const int32_t* t_pos,
+                                   const float* t_a, int32_t heads, int64_t n_src, int64_t nnz, const int32_t* plan,
+                                   const int32_t* counts_host, const int32_t* argmax, int64_t lda, const float* dY,
+                                   int64_t ldy, int32_t d, float* dV, int64_t ldv, void* ws, size_t ws_bytes,
+                                   mp_stream_t stream) {
+  if (!t_a) return MP_ERR_INVALID_ARG;
+  return max_bwd_pull_common<F32>(t_rowptr, t_col, t_pos, t_a, n_src, nnz, plan, counts_host, heads, argmax, lda, dY,
+                                  ldy, d, dV, ldv, ws, ws_bytes, as_stream(stream));
 }
 
 }  // extern "C"

@@ -25,7 +25,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.library import custom_op, register_autograd
 
-from . import placement
+from . import ops, placement
 from ._lib import K, check, lib, ptr
 from .graph import _require_hip, _stream
 
@@ -672,6 +672,19 @@ def _op_ce_bwd_raw(logits: Tensor, labels: Tensor, index: Optional[Tensor], gsca
     idx = None if index is None else index.to(torch.int64).contiguous()
     g = gscale.to(torch.float32).reshape(1).contiguous()
     _check_ce_shapes(z, y, idx)
+    if idx is not None and ops.deterministic():
+        # the per-selected-row gradients [n_sel, C] by the kernel's non-accumulating form on the gathered rows (a row
+        # with an invalid label or index stays zero), then summed per logit row over the index's inverted list on the
+        # aggregation kernel: no float atomics, a row listed several times gets its terms in list order
+        n, n_sel = z.size(0), y.numel()
+        ok = (idx >= 0) & (idx < n)
+        zs = z.index_select(0, torch.where(ok, idx, torch.zeros_like(idx)))
+        ys = torch.where(ok, y, torch.full_like(y, -1))
+        ds = torch.zeros((n_sel, z.size(1)), dtype=torch.float32, device=z.device)
+        with torch.cuda.device(z.device):
+            check(lib().mp_softmax_ce_bwd_f32(ptr(zs), zs.stride(0), n_sel, ptr(ys), None, n_sel, z.size(1), ptr(g),
+                                              float(inv_n), ptr(ds), ds.stride(0), _stream()), "mp_softmax_ce_bwd_f32")
+        return ops._sum_rows_by_ids(idx, n, ds, clamp=True)
     # with an index the rows accumulate onto zeros (a row listed twice gets both terms); without one every row of the
     # first n_sel is written once and the rest must still be zero
     d = torch.zeros_like(z) if (idx is not None or y.numel() < z.size(0)) else torch.empty_like(z)

@@ -29,6 +29,37 @@ from ._lib import check, lib, ptr
 from .graph import CSRGraph, _require_hip, _stream, tensor_stamp
 
 
+# ---- the deterministic switch ----------------------------------------------------------------------
+# The backwards that scatter with float atomics (max through the argmax, gather_rows / index_add_rows with repeated
+# ids, the cross-entropy over a repeated index, the by-node sums of the attention scores) have a second form without
+# them: a gather over an inverted index on the aggregation kernel, the same bits every run.  The choice is made here,
+# where the backward is dispatched, never inside a kernel; with the switch off every op launches what it always did.
+def _env_deterministic():
+    v = os.environ.get("MP_DETERMINISTIC")
+    if v is None or v == "":
+        return None
+    if v not in ("0", "1"):
+        raise ValueError(f"MP_DETERMINISTIC must be 0 or 1, got {v!r}")
+    return v == "1"
+
+
+_DETERMINISTIC = _env_deterministic()       # None: follow torch.are_deterministic_algorithms_enabled()
+
+
+def set_deterministic(mode):
+    """True / False: the engine's reproducible backward forms on / off, whatever torch's flag says; None (the default,
+    unless MP_DETERMINISTIC=0|1 was set at import): follow torch.use_deterministic_algorithms (warn_only or not)"""
+    global _DETERMINISTIC
+    if mode is not None and not isinstance(mode, bool):
+        raise TypeError(f"set_deterministic takes True, False or None, got {mode!r}")
+    _DETERMINISTIC = mode
+
+
+def deterministic():
+    """do the backward passes run their atomics-free forms?"""
+    return torch.are_deterministic_algorithms_enabled() if _DETERMINISTIC is None else _DETERMINISTIC
+
+
 def _f32c(t, name):
     _require_hip(t, name)
     if t.dtype != torch.float32:
@@ -478,17 +509,65 @@ def sage_concat(g, x, Ws, Wn, bias=None, relu=False):
     return concat_dense(x, spmm(g, x, "mean"), Ws, Wn, bias, relu=relu)
 
 
+_IDS_OPS = {}
+
+
+def _ids_operator(ids, n, clamp=False):
+    """the [n x K] operator of an id list ids [K] int64 with entries in [0, n): row r holds the positions k with
+    ids[k] == r in ascending order (a stable sort, then rowptr by binary search: no atomics).  Summing rows u [K, d]
+    over it on the aggregation kernel is index_add over ids in a fixed order.  Cached per id tensor (tensor_stamp).
+    clamp: an id outside [0, n) is listed under row 0 (the caller hands a zero row for it)."""
+    stamp = (tensor_stamp(ids), int(n), bool(clamp))
+    hit = _IDS_OPS.get(stamp)
+    if hit is None:
+        if len(_IDS_OPS) > 8:
+            _IDS_OPS.clear()
+        order = torch.sort(torch.where((ids >= 0) & (ids < n), ids, torch.zeros_like(ids)) if clamp else ids, stable=True)
+        rowptr = torch.searchsorted(order.values, torch.arange(n + 1, dtype=ids.dtype, device=ids.device))
+        op = CSRGraph(rowptr.to(torch.int32), order.indices.to(torch.int32), None, None, n, ids.numel(), ids.numel())
+        hit = _IDS_OPS[stamp] = (op, ids)         # holding `ids` keeps its address from being reused
+    return hit[0]
+
+
+def _sum_rows_by_ids(ids, n, u, clamp=False):
+    """out[r] = sum of u[k] over the k with ids[k] == r, k ascending -> [n, d]: the deterministic index_add"""
+    return _raw_spmm(_ids_operator(ids, n, clamp), u, _lib.SUM)[0]
+
+
+def _entry_sums(g, ds, by_source):
+    """ds [nnz, H] fp32 summed over the entries of every destination (an [N x nnz] operator over g.rowptr, col = arange)
+    or of every source (the same over the transposed pattern's rowptr, col = its pos) on the aggregation kernel: the
+    by-node sums of a per-entry gradient in a fixed order.  Both operators are cached on the graph and share the plan
+    of the pattern they stand on."""
+    key = "_entry_sum_src" if by_source else "_entry_sum_dst"
+    op = g.__dict__.get(key)
+    if op is None:
+        if by_source:
+            gt = g._transpose_sorted()
+            op = CSRGraph(gt.rowptr, gt.pos, None, None, gt.num_nodes, g.nnz, g.nnz)
+            op._plan = gt.plan()
+        else:
+            op = CSRGraph(g.rowptr, torch.arange(g.nnz, dtype=torch.int32, device=g.device), None, None, g.num_nodes,
+                          g.nnz, g.nnz)
+            op._plan = g.plan()
+        g.__dict__[key] = op
+    return _raw_spmm(op, ds.contiguous(), _lib.SUM)[0]
+
+
 class _IndexAddRows(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h, id_index, u):
-        h = _f32c(h, "h").clone()
         u = _f32c(u, "u")
-        L = lib()
         ids = id_index.to(torch.int64).contiguous()
+        ctx.save_for_backward(ids)
+        if deterministic():
+            h = _f32c(h, "h")
+            return h + _sum_rows_by_ids(ids, h.size(0), u)
+        h = _f32c(h, "h").clone()
+        L = lib()
         with torch.cuda.device(h.device):
             check(L.mp_rows_scatter_add_f32(ptr(h), h.stride(0), ptr(ids), ids.numel(), h.size(1),
                                             ptr(u), u.stride(0), _stream()), "mp_rows_scatter_add_f32")
-        ctx.save_for_backward(ids)
         return h
 
     @staticmethod
@@ -523,6 +602,8 @@ class _GatherRows(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         (ids,) = ctx.saved_tensors
+        if deterministic():
+            return _sum_rows_by_ids(ids, ctx.n, _f32c(dout, "dout")), None
         dx = torch.zeros((ctx.n, dout.size(1)), dtype=torch.float32, device=dout.device)
         L = lib()
         dout = dout.contiguous()
@@ -711,6 +792,9 @@ class _SddmmAdd(torch.autograd.Function):
         (s,) = ctx.saved_tensors
         g = ctx.g
         gs = ds.reshape(-1) * torch.where(s > 0, torch.ones_like(s), torch.full_like(s, ctx.slope))
+        if deterministic():
+            gs = gs.view(-1, 1)
+            return _entry_sums(g, gs, False).view(-1), _entry_sums(g, gs, True).view(-1), None, None
         dai = torch.zeros(g.num_nodes, dtype=torch.float32, device=s.device)
         daj = torch.zeros(g.num_nodes, dtype=torch.float32, device=s.device)
         dai.index_add_(0, g.row_ids().long(), gs)
@@ -752,10 +836,11 @@ def _alpha_bwd(g, alpha, dalpha, a_dst, a_src, a_edge, slope, which):
         pre = pre + (ae if has is None else torch.where(has[:, None], ae, torch.zeros_like(ae)))
     ds = ds * torch.where(pre > 0, torch.ones_like(pre), torch.full_like(pre, slope))
     d_dst = d_src = d_edge = None
+    det = deterministic()
     if which & _EA_DST and a_dst is not None:
-        d_dst = torch.zeros_like(a_dst).index_add_(0, rows, ds)
+        d_dst = _entry_sums(g, ds, False) if det else torch.zeros_like(a_dst).index_add_(0, rows, ds)
     if which & _EA_SRC:
-        d_src = torch.zeros_like(a_src).index_add_(0, cols, ds)
+        d_src = _entry_sums(g, ds, True) if det else torch.zeros_like(a_src).index_add_(0, cols, ds)
     if which & _EA_EDGE and a_edge is not None:
         d_edge = torch.zeros_like(a_edge)
         if a_edge.size(0):
@@ -856,8 +941,12 @@ def _mean_dy(g, dy):
 
 def _heads_grad_by_source(g, w, like, heads, is_max, dy, argmax=None):
     """the gradient of the operand gathered by source, shaped like `like`: max scatters w * dy through the argmax into
-    zeros (float atomics; nothing to launch without entries), sum aggregates dy over the transposed pattern with w
+    zeros (float atomics; nothing to launch without entries) — under deterministic() it gathers them over the
+    transposed pattern (mp::spmm_heads_max_bwd_pull_raw) —, sum aggregates dy over the transposed pattern with w
     permuted to its order; a mean's dy comes pre-divided (_mean_dy)"""
+    if is_max and deterministic():
+        from . import maxbwd_ops           # (imports this module: bound late); mp::spmm_heads_max_bwd_pull_raw's launcher
+        return maxbwd_ops._raw_heads_max_bwd_pull(g, dy, argmax, w, heads)
     if is_max:
         dV = torch.zeros_like(like)
         if g.nnz:
@@ -923,6 +1012,8 @@ def spmm_edge_values(g, a, V, heads=1, reduce="sum"):
 #
 #   mp::spmm            y = act(reduce_j w_ij x_j + s x_i + b)         SparseAdj.matmul, sparse_adj.py:91-97
 #       spmm_raw (any graph variant, argmax on request), spmm_rows_raw, spmm_max_bwd_raw
+#       (the max backward without atomics, deterministic(): spmm_max_bwd_pull_raw / spmm_heads_max_bwd_pull_raw of
+#       graphgym_amd/maxbwd_ops.py)
 #   mp::idgnn_agg       (P, Q) = (A x, A S x)                          gcn_id two-branch form, TfgIDLayer.py:510-517
 #       idgnn_agg_raw
 #   mp::agg_dense       act((A x + s x) W + b), one launch             aggregate -> kernel product, TfgIDLayer.py:510-523
@@ -1048,10 +1139,14 @@ def _transposed_variant(reduce):
 
 def _grad_by_source(graph, reduce, dy, argmax, self_scale=0.0):
     """the gradient of the operand a plain aggregation gathers by source (spmm; x of spmm_edge and spmm_code): max scatters
-    dy through the argmax (float atomics), sum and mean run the same kernel on the transposed operator; a self term
+    dy through the argmax (float atomics; under deterministic() the pull form gathers it), sum and mean run the same kernel on the transposed operator; a self term
     self_scale * x[i] adds self_scale * dy"""
     if reduce == _lib.MAX:
-        dx = torch.ops.mp.spmm_max_bwd_raw(dy, argmax, graph)
+        if deterministic():
+            from . import maxbwd_ops  # noqa: F401  (registers the op; imports this module: bound late)
+            dx = torch.ops.mp.spmm_max_bwd_pull_raw(dy, argmax, graph)
+        else:
+            dx = torch.ops.mp.spmm_max_bwd_raw(dy, argmax, graph)
         return dx + self_scale * dy if self_scale != 0.0 else dx
     return torch.ops.mp.spmm_raw(dy, graph, _transposed_variant(reduce), _lib.SUM, dy if self_scale != 0.0 else None,
                                  self_scale, None, False, False)[0]
